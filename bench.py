@@ -48,7 +48,16 @@ runs three phases of child processes (one per GPU), then prints ONE JSON line.
 Phases 2-3 are bounded (``--extras-timeout``); if one fails its keys are null
 and ``extras_error`` says why -- the headline is never lost to them.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+  A plain run does the headline only: set up, W warmup rounds, K timed rounds,
+  the result line.  --full adds everything else described above: the unloaded
+  p50 rounds and the recomputation check of the last round, the in-rank extras
+  (serial collectives, strong scaling, the other precision / fp32 kernels,
+  numerics against fp64, B=50, AlexNet, ResNet50, scatter) and phases 2-3.
+  --dump-outputs DIR: the top-1 (class, probability) arrays the coordinator
+  received for the last timed round, as DIR/top1_class.npy and
+  DIR/top1_prob.npy (float32, one entry per image of the round in image order;
+  same arguments -> same images and weights, so two builds compare 1:1).
   Without torchrun env vars the launcher starts the N ranks itself (RCCL over
   127.0.0.1 rendezvous); under torchrun (RANK set) each torchrun process
   starts its own rank child, and rank 0's launcher runs phases 2-3 on all N
@@ -116,8 +125,14 @@ def parse(argv=None):
                     help="how rank host threads wait for the GPU: spin (HIP synchronize), or poll (event "
                          "query + sleep, at most 2 rounds queued ahead); auto = poll for N > 1 (N rank "
                          "processes plus their RCCL proxy threads must not spin every CPU of the box)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the strong-scaling / fp16 / numerics extras")
-    ap.add_argument("--no-system", action="store_true", help="skip phases 2-3 (system + failover)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: unloaded p50 rounds, the recomputation "
+                         "check, the in-rank extras and phases 2-3 (off: warmup, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed round's top-1 classes and probabilities to DIR/*.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the strong-scaling / fp16 / numerics extras")
+    ap.add_argument("--no-system", action="store_true", help="--full without phases 2-3 (system + failover)")
     ap.add_argument("--node-phases", default="system,failover,worker",
                     help="node phases to run after the headline (comma list of system, failover, worker)")
     ap.add_argument("--extras-timeout", type=float, default=150.0,
@@ -153,7 +168,10 @@ def parse(argv=None):
     ap.add_argument("--worker-kill-chunks", type=lambda v: [int(x) for x in v.split(",")], default=[1, 4, 8],
                     help="chunks in flight on the killed worker, one cluster per value (report Fig 4)")
     ap.add_argument("--work-dir", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.full:
+        a.no_extras = a.no_system = True
+    return a
 
 
 # ---------------------------------------------------------------------------
@@ -656,9 +674,27 @@ def run_rank(a) -> int:
             posted.clear()
         return run, finish
 
+    last_round = {"q": None, "cls": None, "prob": None}
+
+    def dump_outputs() -> None:
+        """--dump-outputs (coordinator): what the timed path handed back for its
+        last timed round, one float32 entry per image in image order."""
+        if not a.dump_outputs or not coord:
+            return
+        assert last_round["cls"] is not None, "the last timed round was never recorded"
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "top1_class.npy"), last_round["cls"])
+        np.save(os.path.join(a.dump_outputs, "top1_prob.npy"), last_round["prob"])
+
     def record_round(state, res, tab, t1):
         """Coordinator: one gathered round (host int32 [W, max_chunk, 2]) into the job state."""
         cls_all, prob_all = res[:, :, 0], res[:, :, 1].view(np.float32)
+        if tab and tab[0][1] == last_round["q"]:
+            # --dump-outputs: the headline's last timed round as the coordinator received it
+            rows = [(cls_all[r, :row[3] - row[2] + 1], prob_all[r, :row[3] - row[2] + 1])
+                    for r, row in enumerate(tab)]
+            last_round["cls"] = np.concatenate([c for c, _ in rows]).astype(np.float32)
+            last_round["prob"] = np.concatenate([p for _, p in rows]).astype(np.float32)
         for r, row in enumerate(tab):
             n = row[3] - row[2] + 1
             state.record_result(a.model, row[1], f"rank{r}", row[2], row[3], cls_all[r, :n].copy(),
@@ -709,9 +745,10 @@ def run_rank(a) -> int:
             cpu_stats[:] = [cpu_rank, _cgroup_delta(cg0, cg1, elapsed)]
         p50_loaded = statistics.median(lat) if lat else None
         lat.clear()
-        for q in range(warmup + steps, warmup + steps + max(5, min(steps, 20))):
-            step(q, False)
-            drain()
+        if a.full:
+            for q in range(warmup + steps, warmup + steps + max(5, min(steps, 20))):
+                step(q, False)
+                drain()
         p50 = statistics.median(lat) if lat else None
         return elapsed, per_rank, p50_loaded, p50
 
@@ -733,7 +770,9 @@ def run_rank(a) -> int:
         step, drain, gtimes, timing = (pipelined_round if pipelined else serial_round)(
             run, per_round, warmup, state, host, lat, pending)
         cpu_stats = []
+        last_round["q"] = warmup + steps - 1 if label == "weak" and a.dump_outputs else None
         elapsed, per_rank, p50_loaded, p50 = run_phases(step, drain, lat, steps, warmup, timing, cpu_stats)
+        last_round["q"] = None
         g_us = ([1000.0 * g0.elapsed_time(g1) for g0, g1 in gtimes] if gpu else [1e6 * x for x in gtimes]) \
             if gtimes else []
         recorded = state.images_done(a.model) if coord else None
@@ -742,7 +781,7 @@ def run_rank(a) -> int:
                 "rank_ms": [1000.0 * x / steps for x in per_rank],
                 "cpu": cpu_stats,
                 "gather_us": statistics.median(g_us) if g_us else None,
-                "verified": verify(state, runner)}
+                "verified": verify(state, runner) if a.full else None}
 
     ahead = {}      # poll mode: round -> event after its forward (the host queues <= 2 rounds ahead)
 
@@ -923,6 +962,7 @@ def run_rank(a) -> int:
     progress("model ready")
     head = measure(make(runner, B), W * B, a.steps, a.warmup, "weak", pipelined=pipe, runner=runner)
     progress("headline measured")
+    dump_outputs()
     extras = {"pipelined_collectives": pipe}
     t_extras = time.perf_counter()
     skipped = []
@@ -956,7 +996,7 @@ def run_rank(a) -> int:
     if a.hang_in_extras == env.rank:
         print(f"bench: rank {env.rank} hanging in the extras on purpose", file=sys.stderr, flush=True)
         time.sleep(3600)
-    if pipe and budget_left("serial collectives"):
+    if a.full and pipe and budget_left("serial collectives"):
         # the same rounds with the broadcast and gather between the forwards on the
         # compute stream: what the pipelining saves, and the gather's own time
         serial = measure(make_run(runner, B), W * B, a.steps, a.warmup, "weak-serial")

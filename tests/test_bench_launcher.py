@@ -31,7 +31,7 @@ def _line(out: str) -> dict:
 @pytest.mark.parametrize("n", [1, 2, 8])
 def test_bench_self_launch_dry_run(n):
     steps, warmup = 3, 1
-    r = _run("--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup), "--ref-delay-queries", "1")
+    r = _run("--full", "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup), "--ref-delay-queries", "1")
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == n
@@ -144,7 +144,7 @@ def test_bench_under_torchrun_dry_run():
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--dry-run", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -156,7 +156,7 @@ def test_bench_under_torchrun_dry_run():
 def test_bench_headline_survives_rank_failure_after_headline():
     """VERDICT r4 item 3: rank 0 writes the headline as soon as it is measured;
     a rank that dies in an extra cannot take the line with it."""
-    r = _run("--gpus", "8", "--steps", "2", "--warmup", "1", "--fail-after-headline", "5", timeout=300)
+    r = _run("--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--fail-after-headline", "5", timeout=300)
     assert "failing after the headline on purpose" in r.stderr
     d = _line(r.stdout)
     assert d["value"] > 0 and d["n_gpus"] == 8 and d["results_verified"] is True
@@ -168,7 +168,7 @@ def test_bench_headline_survives_rank_failure_after_headline():
 def test_bench_headline_survives_rank_hang_in_extras():
     """A rank that hangs in an extra: the launcher's time limit ends the ranks
     and still prints the headline rank 0 wrote (the driver's lease is 600 s)."""
-    r = _run("--gpus", "8", "--steps", "2", "--warmup", "1", "--hang-in-extras", "2", "--launch-timeout", "45",
+    r = _run("--full", "--gpus", "8", "--steps", "2", "--warmup", "1", "--hang-in-extras", "2", "--launch-timeout", "45",
              timeout=300)
     assert "hanging in the extras on purpose" in r.stderr
     d = _line(r.stdout)
@@ -181,3 +181,32 @@ def test_bench_rank_failure_before_headline_prints_error_line():
     assert r.returncode != 0
     d = _line(r.stdout)
     assert d["value"] is None and "before the headline" in d["error"]
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_round(n, tmp_path):
+    """Without --full: warmup + EXACTLY --steps timed rounds and the line (no
+    unloaded rounds, no recomputation check, no extras, no phases 2-3);
+    --dump-outputs writes the last timed round's top-1 arrays (float32, image
+    order).  The fake forward's class is the global image index % 1000."""
+    import numpy as np
+
+    steps, warmup = 3, 2
+    out = tmp_path / "dump"
+    r = _run("--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == n
+    assert d["results_recorded"] == (warmup + steps) * 400 * n
+    assert d["value"] > 0 and d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 400 * n / d["ms_per_step"] * 1e3) <= 0.01 * d["value"]
+    for k in ("results_verified", "images_per_s_strong", "value_serial_collectives", "value_system",
+              "coord_failover_recovery_s", "worker_failover_recovery_s", "extras_wall_s"):
+        assert k not in d, k
+    cls, prob = np.load(out / "top1_class.npy"), np.load(out / "top1_prob.npy")
+    assert sorted(p.name for p in out.iterdir()) == ["top1_class.npy", "top1_prob.npy"]
+    assert cls.dtype == np.float32 and prob.dtype == np.float32 and cls.shape == prob.shape == (400 * n,)
+    # round q reads per_round images from q * per_round, wrapped inside the 2000-image dataset
+    first = ((warmup + steps - 1) * 400 * n) % (2000 - 400 * n + 1)
+    assert np.array_equal(cls, (np.arange(first, first + 400 * n) % 1000).astype(np.float32))
+    assert np.all(prob == 0.5)

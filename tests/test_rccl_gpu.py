@@ -111,7 +111,7 @@ def test_bench_worker_failover_rehearsal_over_rccl(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / "line.json"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-rccl",
-                        "--steps", "3", "--warmup", "1", "--no-extras", "--node-phases", "worker",
+                        "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--node-phases", "worker",
                         "--worker-kill-chunks", "1", "--json-out", str(out)],
                        capture_output=True, text=True, timeout=240, cwd=root)
     assert r.returncode == 0 and out.exists(), (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

@@ -15,7 +15,7 @@ for s in $STEPS; do
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1 || exit 11 ;;
     tests) timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread \
              > $OUT/${TAG}_gpu_tests.log 2>&1 || exit 12 ;;
-    bench) timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.log 2>&1 || exit 13 ;;
+    bench) timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.log 2>&1 || exit 13 ;;
     prof)  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_prof -o run -- \
              python -u tools/fwd_loop.py --model resnet18 --batch 400 --iters 30 > $OUT/${TAG}_prof.log 2>&1 || exit 14 ;;
     hostcost)  # coordinator host cost per round, gloo dry run (CPU only) at N=1 and N=8
