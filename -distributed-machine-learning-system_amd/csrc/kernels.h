@@ -230,4 +230,34 @@ void splitk_reduce_launch(const float* part, int S, long MN, int N, const float*
 void softmax_top1_launch(const float* logits, int ld, int N, int rows, int* cls, float* prob, int* packed,
                          const int* ovf, hipStream_t st);
 
+// ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
+// One descriptor per image on the device; the host (bindings.cpp jpeg_plan) has
+// checked every offset and extent in it against the buffers the kernels get.
+struct alignas(16) JpegImageDesc {
+  unsigned short q[3][64];   // quantisation tables, natural order
+  long long plane_off[3];    // component plane: byte offset (multiple of 16), pitch[c] bytes per row, 8 * bh rows
+  long long out_off;         // byte offset of this image's [out_h][out_w][3] pixels
+  int blk_off[3];            // first 8x8 block of each component in the coefficient buffer
+  int bw[3], bh[3];          // padded block grid
+  int pitch[3];              // plane pitch: 8 * bw rounded up to 16 (a lane stores two blocks' rows at once)
+  int cw[3], ch[3];          // the plane's valid (downsampled) size: ceil(W h / hmax) x ceil(H v / vmax)
+  int W, H, ncomp;
+  int mode;                  // chroma: 0 full size, 1 half width (h2v1), 2 half width and height (h2v2)
+  int rw, rh;                // size after the resize (W, H: no resize)
+  int left, top;             // crop origin in the resized image
+  int out_w, out_h;
+};
+// One per (image, component), ascending in pair_start.  The IDCT's unit of work is a pair of
+// horizontally adjacent blocks (2k, 2k + 1) of one block row: ceil(bw / 2) * bh pairs per segment;
+// the second block of a row's last pair does not exist when bw is odd (it fills plane padding).
+struct JpegSeg {
+  int pair_start, img, comp, pad;
+};
+// coefficients -> uint8 component planes; nslots = 2 * (pairs of all nseg segments) block slots
+void jpeg_idct_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs, int nseg,
+                      int nslots, hipStream_t st);
+// planes -> RGB, resized and cropped: nimg images of at most max_pix output pixels each
+void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,
+                             hipStream_t st);
+
 }  // namespace idunno

@@ -1,0 +1,397 @@
+// Baseline JPEG marker parser and Huffman decoder (see jpeg_entropy.h).
+//
+// Every read of the input goes through a bounds check against the span's end
+// and every write of a coefficient through an index check (k <= 63 inside a
+// block that the header-derived layout places inside the output span), so
+// arbitrary bytes give a status, never an out-of-range access.
+#include "jpeg_entropy.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+namespace idunno {
+
+namespace {
+
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+constexpr int kLookBits = 9;
+
+struct Huff {
+  bool defined = false;
+  int nvals = 0;
+  uint8_t vals[256];
+  uint16_t look[1 << kLookBits];   // (length << 8) | symbol for codes of <= kLookBits bits, else 0
+  int32_t maxcode[17];             // largest code of each length, -1: none
+  int32_t mincode[17];
+  int32_t valptr[17];
+};
+
+// counts[1..16] then the symbols; returns bytes consumed or -1
+int build_huff(const uint8_t* seg, size_t slen, Huff* h) {
+  if (slen < 16) return -1;
+  int counts[17];
+  int total = 0;
+  for (int l = 1; l <= 16; ++l) {
+    counts[l] = seg[l - 1];
+    total += counts[l];
+  }
+  if (total > 256 || (size_t)(16 + total) > slen) return -1;
+  std::memcpy(h->vals, seg + 16, (size_t)total);
+  h->nvals = total;
+  std::memset(h->look, 0, sizeof(h->look));
+  int32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    if (code + counts[l] > (1 << l)) return -1;        // more codes than the length has room for
+    h->valptr[l] = k;
+    h->mincode[l] = code;
+    h->maxcode[l] = counts[l] ? code + counts[l] - 1 : -1;
+    if (l <= kLookBits) {
+      for (int i = 0; i < counts[l]; ++i) {
+        const int first = (code + i) << (kLookBits - l);
+        for (int j = 0; j < (1 << (kLookBits - l)); ++j)
+          h->look[first + j] = (uint16_t)((l << 8) | h->vals[k + i]);
+      }
+    }
+    k += counts[l];
+    code = (code + counts[l]) << 1;
+  }
+  h->defined = true;
+  return 16 + total;
+}
+
+struct Tables {
+  bool qdef[4] = {false, false, false, false};
+  uint16_t q[4][64];
+  Huff dc[4], ac[4];
+};
+
+struct Scan {
+  int td[3], ta[3];
+};
+
+inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) {
+  if (data == nullptr || n == 0) return JPEG_EMPTY;
+  if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_NOT_JPEG;
+  std::memset(hdr, 0, sizeof(*hdr));
+  bool have_sof = false;
+  int comp_id[3] = {0, 0, 0};
+  size_t pos = 2;
+  for (;;) {
+    if (pos + 2 > n || data[pos] != 0xFF) return JPEG_CORRUPT;
+    while (pos < n && data[pos] == 0xFF) ++pos;         // fill bytes
+    if (pos >= n) return JPEG_CORRUPT;
+    const int m = data[pos++];
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // stand-alone markers
+    if (m == 0xD8 || m == 0xD9 || m == 0x00) return JPEG_CORRUPT;
+    if (pos + 2 > n) return JPEG_CORRUPT;
+    const int L = be16(data + pos);
+    if (L < 2 || pos + (size_t)L > n) return JPEG_CORRUPT;
+    const uint8_t* seg = data + pos + 2;
+    const size_t slen = (size_t)L - 2;
+    pos += (size_t)L;
+    switch (m) {
+      case 0xC2:
+        return JPEG_UNSUPPORTED_PROGRESSIVE;
+      case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC8:
+        return JPEG_UNSUPPORTED_SOF;
+      case 0xC9: case 0xCA: case 0xCB: case 0xCC: case 0xCD: case 0xCE: case 0xCF:
+        return JPEG_UNSUPPORTED_ARITHMETIC;
+      case 0xC0: case 0xC1: {
+        if (have_sof || slen < 6) return JPEG_CORRUPT;
+        if (seg[0] != 8) return JPEG_UNSUPPORTED_PRECISION;
+        const int H = be16(seg + 1), W = be16(seg + 3), nf = seg[5];
+        if (nf != 1 && nf != 3) return nf == 0 ? JPEG_CORRUPT : JPEG_UNSUPPORTED_COMPONENTS;
+        if (slen != (size_t)(6 + 3 * nf) || W == 0 || H == 0) return JPEG_CORRUPT;
+        if (W > kJpegMaxDim || H > kJpegMaxDim) return JPEG_UNSUPPORTED_SIZE;
+        hdr->W = W;
+        hdr->H = H;
+        hdr->ncomp = nf;
+        for (int c = 0; c < nf; ++c) {
+          comp_id[c] = seg[6 + 3 * c];
+          const int hv = seg[7 + 3 * c], tq = seg[8 + 3 * c];
+          const int h = hv >> 4, v = hv & 15;
+          if (h < 1 || h > 4 || v < 1 || v > 4 || tq > 3) return JPEG_CORRUPT;
+          hdr->comp[c].h = nf == 1 ? 1 : h;             // one component: never interleaved
+          hdr->comp[c].v = nf == 1 ? 1 : v;
+          hdr->comp[c].qidx = tq;
+        }
+        if (nf == 3) {
+          const JpegComp* cp = hdr->comp;
+          if (cp[1].h != cp[2].h || cp[1].v != cp[2].v) return JPEG_UNSUPPORTED_SAMPLING;
+          if (cp[0].h == cp[1].h && cp[0].v == cp[1].v) hdr->mode = 0;
+          else if (cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 2 && cp[0].v == 1) hdr->mode = 1;
+          else if (cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 2 && cp[0].v == 2) hdr->mode = 2;
+          else return JPEG_UNSUPPORTED_SAMPLING;
+        }
+        hdr->hmax = hdr->comp[0].h;
+        hdr->vmax = hdr->comp[0].v;
+        hdr->mcux = (W + 8 * hdr->hmax - 1) / (8 * hdr->hmax);
+        hdr->mcuy = (H + 8 * hdr->vmax - 1) / (8 * hdr->vmax);
+        uint32_t off = 0;
+        for (int c = 0; c < nf; ++c) {
+          JpegComp& cp = hdr->comp[c];
+          cp.bw = hdr->mcux * cp.h;
+          cp.bh = hdr->mcuy * cp.v;
+          cp.coef_off = off;
+          off += (uint32_t)cp.bw * (uint32_t)cp.bh * 64u;
+        }
+        hdr->total_coefs = off;
+        have_sof = true;
+        break;
+      }
+      case 0xDB: {
+        size_t p = 0;
+        while (p < slen) {
+          const int pq = seg[p] >> 4, tq = seg[p] & 15;
+          if (pq == 1) return JPEG_UNSUPPORTED_QUANT16;
+          if (pq != 0 || tq > 3 || p + 65 > slen) return JPEG_CORRUPT;
+          for (int k = 0; k < 64; ++k) tb->q[tq][kZigzag[k]] = seg[p + 1 + k];
+          tb->qdef[tq] = true;
+          p += 65;
+        }
+        break;
+      }
+      case 0xC4: {
+        size_t p = 0;
+        while (p < slen) {
+          const int tc = seg[p] >> 4, th = seg[p] & 15;
+          if (tc > 1 || th > 3) return JPEG_CORRUPT;
+          const int used = build_huff(seg + p + 1, slen - p - 1, tc ? &tb->ac[th] : &tb->dc[th]);
+          if (used < 0) return JPEG_CORRUPT;
+          p += 1 + (size_t)used;
+        }
+        break;
+      }
+      case 0xDD:
+        if (slen != 2) return JPEG_CORRUPT;
+        hdr->restart_interval = be16(seg);
+        break;
+      case 0xDA: {
+        if (!have_sof || slen < 1) return JPEG_CORRUPT;
+        const int ns = seg[0];
+        if (ns < 1 || ns > 4 || slen != (size_t)(4 + 2 * ns)) return JPEG_CORRUPT;
+        if (ns != hdr->ncomp) return JPEG_UNSUPPORTED_MULTISCAN;
+        for (int c = 0; c < ns; ++c) {
+          if (seg[1 + 2 * c] != comp_id[c]) return JPEG_CORRUPT;
+          const int t = seg[2 + 2 * c];
+          sc->td[c] = t >> 4;
+          sc->ta[c] = t & 15;
+          if (sc->td[c] > 3 || sc->ta[c] > 3) return JPEG_CORRUPT;
+          if (!tb->dc[sc->td[c]].defined || !tb->ac[sc->ta[c]].defined) return JPEG_CORRUPT;
+          if (!tb->qdef[hdr->comp[c].qidx]) return JPEG_CORRUPT;
+          std::memcpy(hdr->comp[c].q, tb->q[hdr->comp[c].qidx], sizeof(hdr->comp[c].q));
+        }
+        const uint8_t* t = seg + 1 + 2 * ns;
+        if (t[0] != 0 || t[1] != 63 || t[2] != 0) return JPEG_CORRUPT;
+        hdr->scan_pos = (uint32_t)pos;
+        return JPEG_OK;
+      }
+      default:                                           // APPn, COM and anything else with a length
+        break;
+    }
+  }
+}
+
+// MSB-first bit reader over the entropy-coded segment: removes byte stuffing,
+// stops at a marker (feeding zero bits the decoder must not consume).
+struct BitReader {
+  const uint8_t* data;
+  size_t p, end;
+  uint64_t acc = 0;
+  int nbits = 0;       // bits in acc
+  int pad = 0;         // of which zero bits made up past a marker / the end (always the lowest)
+  bool stopped = false;
+  bool overrun = false;
+
+  void fill() {
+    while (nbits <= 56) {
+      unsigned b = 0;
+      if (!stopped) {
+        if (p >= end) {
+          stopped = true;
+        } else if (data[p] != 0xFF) {
+          b = data[p++];
+        } else if (p + 1 >= end) {
+          stopped = true;
+        } else if (data[p + 1] == 0x00) {
+          b = 0xFF;
+          p += 2;
+        } else if (data[p + 1] == 0xFF) {
+          ++p;                                           // fill byte
+          continue;
+        } else {
+          stopped = true;                                // a marker: stay on its 0xFF
+        }
+      }
+      if (stopped) pad += 8;
+      acc = (acc << 8) | b;
+      nbits += 8;
+    }
+  }
+  inline void ensure() {
+    if (nbits < 32) fill();
+  }
+  inline unsigned peek(int k) const { return (unsigned)(acc >> (nbits - k)) & ((1u << k) - 1u); }
+  inline void skip(int k) {
+    nbits -= k;
+    if (nbits < pad) {
+      overrun = true;
+      pad = nbits;
+    }
+  }
+  inline unsigned get(int k) {
+    const unsigned v = peek(k);
+    skip(k);
+    return v;
+  }
+  // byte-align and consume RSTn; false: not there
+  bool restart(int idx) {
+    if (nbits - pad >= 8) return false;                  // whole data bytes in front of the marker
+    acc = 0;
+    nbits = pad = 0;
+    stopped = false;
+    if (p + 2 > end || data[p] != 0xFF) return false;
+    while (p < end && data[p] == 0xFF) ++p;
+    if (p >= end || data[p] != 0xD0 + (idx & 7)) return false;
+    ++p;
+    return true;
+  }
+};
+
+// a Huffman symbol, or -1 on a code the table does not hold
+inline int decode_sym(BitReader& br, const Huff& h) {
+  br.ensure();
+  const unsigned e = h.look[br.peek(kLookBits)];
+  if (e) {
+    br.skip((int)(e >> 8));
+    return (int)(e & 255);
+  }
+  const unsigned c16 = br.peek(16);
+  for (int l = kLookBits + 1; l <= 16; ++l) {
+    const int32_t c = (int32_t)(c16 >> (16 - l));
+    if (h.maxcode[l] >= 0 && c <= h.maxcode[l] && c >= h.mincode[l]) {
+      const int idx = h.valptr[l] + (c - h.mincode[l]);
+      if (idx >= h.nvals) return -1;
+      br.skip(l);
+      return h.vals[idx];
+    }
+  }
+  return -1;
+}
+
+inline int receive_extend(BitReader& br, int s) {
+  br.ensure();
+  const int v = (int)br.get(s);
+  return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+// one 8x8 block into blk[64] (zeroed by the caller); false on corruption
+bool decode_block(BitReader& br, const Huff& dc, const Huff& ac, int* pred, int16_t* blk) {
+  int s = decode_sym(br, dc);
+  if (s < 0 || s > 15) return false;
+  if (s) *pred += receive_extend(br, s);
+  if (*pred < -32768 || *pred > 32767) return false;
+  blk[0] = (int16_t)*pred;
+  int k = 1;
+  while (k < 64) {
+    const int rs = decode_sym(br, ac);
+    if (rs < 0) return false;
+    const int r = rs >> 4;
+    s = rs & 15;
+    if (s == 0) {
+      if (r != 15) break;                                // EOB
+      k += 16;                                           // ZRL
+      if (k > 64) return false;
+      continue;
+    }
+    k += r;
+    if (k > 63) return false;
+    blk[kZigzag[k]] = (int16_t)receive_extend(br, s);
+    ++k;
+  }
+  return !br.overrun;
+}
+
+}  // namespace
+
+const char* jpeg_status_name(int status) {
+  static const char* const names[JPEG_STATUS_COUNT] = {
+      "ok", "empty", "not_jpeg", "corrupt", "progressive", "arithmetic", "precision", "components",
+      "quant16", "sampling", "size", "multiscan", "sof", "buffer_too_small"};
+  return status >= 0 && status < JPEG_STATUS_COUNT ? names[status] : "unknown";
+}
+
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr) {
+  std::vector<Tables> tb(1);                             // ~9 KB: off the stack
+  Scan sc;
+  return parse(data, n, hdr, &tb[0], &sc);
+}
+
+int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap) {
+  std::vector<Tables> tbv(1);
+  Tables& tb = tbv[0];
+  Scan sc;
+  const int st = parse(data, n, hdr, &tb, &sc);
+  if (st != JPEG_OK) return st;
+  if (out == nullptr || (size_t)hdr->total_coefs > out_cap) return JPEG_BUFFER_TOO_SMALL;
+  std::memset(out, 0, (size_t)hdr->total_coefs * sizeof(int16_t));
+  BitReader br;
+  br.data = data;
+  br.p = hdr->scan_pos;
+  br.end = n;
+  int pred[3] = {0, 0, 0};
+  const int ri = hdr->restart_interval;
+  int left = ri, rst = 0;
+  for (int my = 0; my < hdr->mcuy; ++my) {
+    for (int mx = 0; mx < hdr->mcux; ++mx) {
+      if (ri) {
+        if (left == 0) {
+          if (!br.restart(rst++)) return JPEG_CORRUPT;
+          pred[0] = pred[1] = pred[2] = 0;
+          left = ri;
+        }
+        --left;
+      }
+      for (int c = 0; c < hdr->ncomp; ++c) {
+        const JpegComp& cp = hdr->comp[c];
+        for (int by = 0; by < cp.v; ++by) {
+          for (int bx = 0; bx < cp.h; ++bx) {
+            const size_t b = (size_t)(my * cp.v + by) * (size_t)cp.bw + (size_t)(mx * cp.h + bx);
+            if (!decode_block(br, tb.dc[sc.td[c]], tb.ac[sc.ta[c]], &pred[c], out + cp.coef_off + b * 64))
+              return JPEG_CORRUPT;
+          }
+        }
+      }
+    }
+  }
+  return JPEG_OK;
+}
+
+void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
+                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads) {
+  std::atomic<int> next{0};
+  auto work = [&]() {
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= n) return;
+      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i]);
+    }
+  };
+  const int nt = std::max(1, std::min(nthreads, n));
+  std::vector<std::thread> th;
+  th.reserve((size_t)nt - 1);
+  for (int i = 1; i < nt; ++i) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+}
+
+}  // namespace idunno

@@ -28,11 +28,14 @@ import time
 import torch
 
 from .models.reference import canonical
-from .runtime.data import JpegSource, SyntheticSource
+from .runtime.data import GpuJpegSource, JpegSource, SyntheticSource
 from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
+# (device, directory) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# index only; after replacing files of a directory call drop_gpu_sources()
+_GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
 
 
@@ -46,11 +49,23 @@ def _executor(device: torch.device, seed: int):
     return ex
 
 
+def drop_gpu_sources() -> None:
+    """Forget the images ``decoder="gpu"`` calls keep resident in HBM."""
+    with _LOCK:
+        _GPU_SOURCES.clear()
+
+
 def deeplearning(filename: str, modelname: str, start_image: int, end_image: int, *,
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
-                 data_seed: int = 1234, root: str = "."):
+                 data_seed: int = 1234, root: str = ".", decoder: str = "pil"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
-    ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference."""
+    ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
+    ``decoder="gpu"`` decodes the JPEG files with the native entropy decoder and
+    the HIP kernels (``GpuJpegSource``: decoded images stay in HBM across calls
+    by index -- ``drop_gpu_sources()`` after replacing files; without a GPU it
+    decodes with Pillow like ``"pil"``)."""
+    if decoder not in ("pil", "gpu"):
+        raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -58,7 +73,15 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     model = canonical(modelname)
     ex = _executor(device, seed)
     d = os.path.join(root, filename)
-    src = JpegSource(device, root=d) if os.path.isdir(d) else SyntheticSource(data_seed, device)
+    if not os.path.isdir(d):
+        src = SyntheticSource(data_seed, device)
+    elif decoder == "gpu":
+        with _LOCK:
+            src = _GPU_SOURCES.get((str(device), os.path.abspath(d)))
+            if src is None:
+                src = _GPU_SOURCES[(str(device), os.path.abspath(d))] = GpuJpegSource(device, root=d)
+    else:
+        src = JpegSource(device, root=d)
     names = class_names()
     n = end_image - start_image + 1
     batch = n if not batch or batch <= 0 else batch
@@ -78,8 +101,11 @@ def main(argv=None) -> int:
     ap.add_argument("--dir", default=None, help="image directory (default: ./<model>, else synthetic)")
     ap.add_argument("--device", default=None)
     ap.add_argument("--batch", type=int, default=0, help="images per forward (1 = reference behaviour)")
+    ap.add_argument("--decoder", default="pil", choices=["pil", "gpu"],
+                    help="JPEG decode: Pillow on host threads, or native entropy decode + HIP kernels")
     a = ap.parse_args(argv)
-    res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch)
+    res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
+                           decoder=a.decoder)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

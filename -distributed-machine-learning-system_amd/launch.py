@@ -36,7 +36,7 @@ def run_node(a) -> int:
     import torch
 
     from .runtime.client import Client
-    from .runtime.data import SdfsSource, SyntheticSource
+    from .runtime.data import GpuJpegSource, SdfsSource, SyntheticSource
     from .runtime.executor import make_executor
     from .runtime.node import Node
     from .runtime.shell import Shell
@@ -59,8 +59,12 @@ def run_node(a) -> int:
             torch.cuda.device_count() >= cfg.num_nodes      # (a single node: one-member rounds)
     tr = TcpTransport(name, cfg.address, cfg.address(name))
     node = Node(cfg, name, tr, ex)
-    node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
-                   else SyntheticSource(cfg.data_seed, dev))
+    if a.source == "jpeg":
+        # real files: `put` test_<i>.JPEG into SDFS, then `inference <start> <end> <model>`
+        node.source = GpuJpegSource(sdfs=node.sdfs, device=dev)
+    else:
+        node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
+                       else SyntheticSource(cfg.data_seed, dev))
     if a.index != cfg.coordinator:
         time.sleep(a.join_delay)
     node.start(join=True)
@@ -113,7 +117,7 @@ def run_cluster(a) -> int:
     return rc
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("mode", choices=["node", "cluster"])
     ap.add_argument("--index", type=int, default=0)
@@ -125,12 +129,16 @@ def main(argv=None) -> int:
     ap.add_argument("--coordinator", type=int, default=None)
     ap.add_argument("--standby", type=int, default=None)
     ap.add_argument("--executor", default="auto", choices=["auto", "hip", "torch", "fake"])
-    ap.add_argument("--source", default="synthetic", choices=["synthetic", "sdfs"])
+    ap.add_argument("--source", default="synthetic", choices=["synthetic", "sdfs", "jpeg"])
     ap.add_argument("--shell", action="store_true")
     ap.add_argument("--shell-node", type=int, default=None)
     ap.add_argument("--no-shell", action="store_true")
     ap.add_argument("--join-delay", type=float, default=0.5)
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
     return run_node(a) if a.mode == "node" else run_cluster(a)
 
 

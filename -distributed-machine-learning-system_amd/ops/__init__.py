@@ -14,6 +14,7 @@ __all__ = [
     "maxpool2d", "global_avgpool", "softmax_top1", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
+    "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
 ]
 
 
@@ -301,3 +302,39 @@ def synth_images(seed: int, start: int, n: int, device, hw: int = 224):
     import torch
 
     return load().synth_images(int(seed), int(start), int(n), int(hw), torch.device(device))
+
+
+# ---- JPEG decode (runtime/jpeg.py drives these) ---------------------------------------
+
+def jpeg_parse(data: bytes):
+    """Markers of a JPEG up to SOS: (status, reason, header dict or None);
+    status 0 = a baseline file the native decoder takes."""
+    return load().jpeg_parse(data)
+
+
+def jpeg_entropy_batch(datas, threads: int = 8):
+    """Huffman-decode a list of ``bytes | None`` on ``threads`` native threads
+    (GIL released): (status per entry, headers, int16 coefficients on the
+    host, first coefficient of each entry or -1)."""
+    return load().jpeg_entropy_batch(datas, int(threads))
+
+
+def jpeg_plan(hdr, status, offs, coef_elems: int, geom, crop: int, device):
+    """Validate a decoded batch against its buffers and build the device
+    descriptor tables; ``geom`` int64 [n, 4] = (rw, rh, left, top) or None for
+    full resolution."""
+    import torch
+
+    return load().jpeg_plan(hdr, status, offs, int(coef_elems), geom, int(crop), torch.device(device))
+
+
+def jpeg_idct(plan, coefs, planes):
+    """Dequantise + 8x8 IDCT of a planned batch: int16 coefficients in HBM ->
+    uint8 component planes (``plan.plane_bytes``)."""
+    load().jpeg_idct(plan, coefs, planes)
+
+
+def jpeg_resize_crop(plan, planes, out):
+    """Component planes -> RGB uint8 in ``out`` (``plan.out_bytes``): chroma
+    upsampling, colour conversion, BILINEAR resize, centre crop."""
+    load().jpeg_resize_crop(plan, planes, out)

@@ -608,6 +608,159 @@ class JpegSource:
         return self.stager.stage(arr, arr.shape)
 
 
+class GpuJpegSource:
+    """``JpegSource`` with the decode moved off the interpreter: the files'
+    Huffman streams are decoded by native host threads, everything after that
+    (IDCT, upsampling, colour conversion, resize, crop) by HIP kernels
+    (runtime/jpeg.py), and the decoded images stay resident in HBM by index, up
+    to ``cache_bytes`` with oldest-first eviction, so a repeated query decodes
+    nothing.  Files the native decoder does not take go through
+    ``load_image_u8``; on a CPU device every file does.  Same ``get`` /
+    ``cached`` / ``missing`` contract as ``JpegSource``, plus ``prefetch``.
+
+    An image that could not be read (not ``put`` yet, no replica answered) is
+    served as zeros and listed in ``missing`` like ``JpegSource`` does, and is
+    NOT cached: the next ``get`` reads it again.  A decoded image is cached by
+    its index alone, not by the file's SDFS version or mtime: a file replaced
+    after its first decode is not seen until ``invalidate`` drops it.
+    ``cache_bytes`` counts images; a cached image is a row of its chunk's
+    tensor (up to ``CHUNK`` images, ~38 MB), which is freed once its last row
+    is evicted, so residency can exceed ``cache_bytes`` by less than one chunk
+    per partly evicted chunk."""
+
+    CHUNK = 256          # images per decode_batch call (bounds the coefficient buffers: ~0.6 MB per 500x375 image)
+
+    def __init__(self, device, root: str | None = None, sdfs=None, prefix: str = "", cache_bytes: int = 16 << 30,
+                 threads: int = 8, resize: int = 256, crop: int = HW):
+        from concurrent.futures import ThreadPoolExecutor
+
+        self.device = torch.device(device)
+        self.root, self.sdfs, self.prefix = root, sdfs, prefix
+        self.cache_bytes = int(cache_bytes)
+        self.threads, self.resize, self.crop = int(threads), int(resize), int(crop)
+        self.stager = HbmStager(self.device) if self.device.type == "cuda" else None
+        self.readers = ThreadPoolExecutor(max_workers=8, thread_name_prefix="jpeg-read")
+        self.cache: OrderedDict[int, tuple] = OrderedDict()     # index -> (chunk tensor, row in it)
+        self.lock = threading.RLock()
+        self.missing: list[int] = []
+        self.decoded = 0            # images decoded (GPU path or fallback)
+        self.fallbacks = 0          # of which by load_image_u8 on the host
+        self.cache_hits = 0         # images served from HBM without a decode
+        self.fallback_reasons: dict[int, str] = {}
+        self.seconds = {"entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0}
+        self._pool = None
+        self._front = None
+
+    _read = JpegSource._read
+
+    def cached(self, start: int, end: int) -> bool:
+        """Every image of [start, end] is resident (get() will decode nothing)."""
+        with self.lock:
+            return all(i in self.cache for i in range(start, end + 1))
+
+    def invalidate(self, start: int | None = None, end: int | None = None) -> None:
+        """Drop the cached images of [start, end] (everything by default), e.g.
+        after their files were replaced; they decode again on the next get()."""
+        with self.lock:
+            if start is None:
+                self.cache.clear()
+            else:
+                for i in range(start, (start if end is None else end) + 1):
+                    self.cache.pop(i, None)
+
+    def prefetch(self, start: int, end: int) -> None:
+        """Start decoding [start, end] into the cache on a background thread."""
+        from concurrent.futures import ThreadPoolExecutor
+
+        with self.lock:
+            if self._pool is None:
+                self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="jpeg-prefetch")
+        dev = self.device
+
+        def run():
+            import contextlib
+
+            with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
+                self.get(start, end)
+        self._pool.submit(run)
+
+    def _decode(self, idx: list[int]) -> tuple[dict, set]:
+        """Decode the images ``idx``: (index -> (chunk tensor, row), the indices
+        that could not be read -- zero rows, never to be cached)."""
+        from . import jpeg
+
+        gpu = self.device.type == "cuda"
+
+        def front(part):
+            # reads + Huffman decode (native threads, no GIL): runs one chunk ahead, under the
+            # previous chunk's host -> HBM copy and kernels
+            datas = list(self.readers.map(self._read, part))
+            return datas, (jpeg.entropy_batch(datas, self.threads) if gpu else None)
+
+        got, absent = {}, set()
+        parts = [idx[c:c + self.CHUNK] for c in range(0, len(idx), self.CHUNK)]
+        if self._front is None:
+            from concurrent.futures import ThreadPoolExecutor
+
+            self._front = ThreadPoolExecutor(max_workers=1, thread_name_prefix="jpeg-entropy")
+        nxt = self._front.submit(front, parts[0])
+        for k, part in enumerate(parts):
+            datas, ent = nxt.result()
+            if k + 1 < len(parts):
+                nxt = self._front.submit(front, parts[k + 1])
+            imgs, info = jpeg.decode_batch(datas, self.device, self.resize, self.crop, self.threads, self.stager,
+                                           entropy=ent)
+            for name in self.seconds:
+                self.seconds[name] += info[name]
+            for j, reason in info["fallbacks"]:
+                self.fallback_reasons[part[j]] = reason
+            self.fallbacks += len(info["fallbacks"])
+            for j, i in enumerate(part):
+                if datas[j] is None:
+                    self.missing.append(i)
+                    absent.add(i)
+                else:
+                    self.decoded += 1
+                got[i] = (imgs, j)
+        return got, absent
+
+    def get(self, start: int, end: int) -> torch.Tensor:
+        idx = list(range(start, end + 1))
+        with self.lock:
+            got = {i: self.cache[i] for i in idx if i in self.cache}
+            self.cache_hits += len(got)
+            todo = [i for i in idx if i not in got]
+            if todo:
+                new, absent = self._decode(todo)
+                got.update(new)
+                # an unreadable file (not put yet, no replica answered) is read again next time
+                self.cache.update((i, v) for i, v in new.items() if i not in absent)
+                per = self.crop * self.crop * 3
+                while len(self.cache) * per > self.cache_bytes and len(self.cache) > 1:
+                    self.cache.popitem(last=False)
+        # runs of consecutive rows of one chunk tensor: a resident range is one view, no copy
+        runs = []
+        for i in idx:
+            t, r = got[i]
+            if runs and runs[-1][0] is t and runs[-1][2] == r:
+                runs[-1][2] = r + 1
+            else:
+                runs.append([t, r, r + 1])
+        if self.device.type == "cuda":
+            cs = torch.cuda.current_stream(self.device)
+            for t, _, _ in runs:
+                t.record_stream(cs)
+        if len(runs) == 1:
+            t, a, b = runs[0]
+            return t[a:b]
+        out = torch.empty((len(idx), self.crop, self.crop, 3), dtype=torch.uint8, device=self.device)
+        k = 0
+        for t, a, b in runs:
+            out[k:k + b - a].copy_(t[a:b], non_blocking=True)
+            k += b - a
+        return out
+
+
 def put_synthetic_dataset(sdfs, n_images: int, seed: int, shard_images: int = 500) -> int:
     """Upload a deterministic synthetic dataset into SDFS as uint8 shards."""
     k = 0

@@ -1,0 +1,281 @@
+"""JPEG decode for the image data path: native entropy decode on host threads,
+IDCT + chroma upsampling + colour conversion + resize + crop on the GPU.
+
+    bytes --(csrc/runtime/jpeg_entropy.cpp, std::threads, no GIL)--> int16 DCT
+    coefficients --(HbmStager: pinned ping-pong, side stream)--> HBM
+    --(kernels/jpeg_decode.hip: jpeg_idct, jpeg_resize_crop)--> uint8 [B,224,224,3]
+
+The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
+(fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
+crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
+decoder does not take (progressive, arithmetic, 12-bit, CMYK, odd sampling,
+corrupt, not a JPEG at all) are decoded by ``load_image_u8`` on the host and
+reported in ``info["fallbacks"]``; on a CPU device every image takes that
+path.  ``reference_backend`` is the float64 numpy model of the GPU chain.
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+import torch
+
+from .data import HbmStager, load_image_u8
+
+_STAGERS: dict = {}
+
+
+def _C():
+    from .. import ops
+
+    ops.load()
+    return ops
+
+
+def parse(data: bytes):
+    """Header of a baseline JPEG the native decoder takes (dict: W, H, ncomp,
+    mode, comp[i] = h, v, bw, bh, coef_off, q), or the reason (str) it does not."""
+    st, reason, hdr = _C().jpeg_parse(bytes(data))
+    return hdr if st == 0 else reason
+
+
+def entropy_decode(data: bytes):
+    """(header, int16 coefficients) of one image by the native host decoder, or
+    the reason (str) it was refused."""
+    data = bytes(data)
+    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1)
+    if status[0] != 0:
+        st, reason, _ = _C().jpeg_parse(data)
+        return reason if st != 0 else "corrupt"
+    return parse(data), coefs.numpy()
+
+
+# ---- float64 model of the GPU chain ------------------------------------------------
+
+def _idct_matrix() -> np.ndarray:
+    x = np.arange(8)[:, None]
+    u = np.arange(8)[None, :]
+    m = 0.5 * np.cos((2 * x + 1) * u * np.pi / 16)
+    m[:, 0] *= np.sqrt(0.5)
+    return m                       # [sample, frequency]
+
+
+def _round_u8(a: np.ndarray) -> np.ndarray:
+    return np.clip(np.floor(a + 0.5), 0, 255)
+
+
+def _upsample_h2v1(p: np.ndarray) -> np.ndarray:
+    p = p.astype(np.int32)
+    left = np.concatenate([p[:, :1], p[:, :-1]], 1)
+    right = np.concatenate([p[:, 1:], p[:, -1:]], 1)
+    out = np.empty((p.shape[0], 2 * p.shape[1]), np.int32)
+    out[:, 0::2] = (3 * p + left + 1) >> 2
+    out[:, 1::2] = (3 * p + right + 2) >> 2
+    out[:, 0] = p[:, 0]
+    out[:, -1] = p[:, -1]
+    return out
+
+
+def _upsample_h2v2(p: np.ndarray) -> np.ndarray:
+    p = p.astype(np.int32)
+    above = np.concatenate([p[:1], p[:-1]], 0)
+    below = np.concatenate([p[1:], p[-1:]], 0)
+    t = np.empty((2 * p.shape[0], p.shape[1]), np.int32)
+    t[0::2] = 3 * p + above
+    t[1::2] = 3 * p + below
+    left = np.concatenate([t[:, :1], t[:, :-1]], 1)
+    right = np.concatenate([t[:, 1:], t[:, -1:]], 1)
+    out = np.empty((t.shape[0], 2 * t.shape[1]), np.int32)
+    out[:, 0::2] = (3 * t + left + 8) >> 4
+    out[:, 1::2] = (3 * t + right + 7) >> 4
+    out[:, 0] = (4 * t[:, 0] + 8) >> 4
+    out[:, -1] = (4 * t[:, -1] + 7) >> 4
+    return out
+
+
+def reference_backend(header: dict, coeffs: np.ndarray) -> np.ndarray:
+    """Full-resolution RGB uint8 [H, W, 3] from a header and its coefficients:
+    exact IDCT in float64, planes cut to their downsampled size, libjpeg's
+    fancy upsampling, colour conversion rounded half up."""
+    W, H = header["W"], header["H"]
+    hmax, vmax = header["hmax"], header["vmax"]
+    m = _idct_matrix()
+    planes = []
+    for c in header["comp"]:
+        bw, bh = c["bw"], c["bh"]
+        f = np.asarray(coeffs[c["coef_off"]:c["coef_off"] + bw * bh * 64], np.float64).reshape(bh, bw, 8, 8)
+        f = f * np.asarray(c["q"], np.float64).reshape(8, 8)
+        px = np.einsum("yv,abvu,xu->aybx", m, f, m).reshape(bh * 8, bw * 8)
+        cw, ch = -(-W * c["h"] // hmax), -(-H * c["v"] // vmax)
+        planes.append(_round_u8(px + 128.0)[:ch, :cw])
+    y = planes[0]
+    if len(planes) == 1:
+        return np.repeat(y[:, :, None], 3, 2).astype(np.uint8)
+    up = {0: lambda p: p, 1: _upsample_h2v1, 2: _upsample_h2v2}[header["mode"]]
+    cb = up(planes[1])[:H, :W].astype(np.float64) - 128.0
+    cr = up(planes[2])[:H, :W].astype(np.float64) - 128.0
+    rgb = np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], 2)
+    return _round_u8(rgb).astype(np.uint8)
+
+
+def _bilinear_weights(n_in: int, n_out: int) -> np.ndarray:
+    """Pillow's BILINEAR as a [n_out, n_in] matrix (rows sum to 1)."""
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    w = np.zeros((n_out, n_in))
+    for i in range(n_out):
+        centre = (i + 0.5) * scale
+        lo, hi = max(0, int(centre - fs + 0.5)), min(n_in, int(centre + fs + 0.5))
+        x = np.arange(lo, hi)
+        k = np.maximum(0.0, 1.0 - np.abs((x - centre + 0.5) / fs))
+        w[i, lo:hi] = k / k.sum()
+    return w
+
+
+def resize_geometry(w: int, h: int, resize: int, crop: int):
+    """(nw, nh, left, top) by the expressions of ``load_image_u8``."""
+    if w <= h:
+        nw, nh = resize, int(resize * h / w)
+    else:
+        nh, nw = resize, int(resize * w / h)
+    return nw, nh, int(round((nw - crop) / 2.0)), int(round((nh - crop) / 2.0))
+
+
+def reference_resize_crop(rgb: np.ndarray, resize: int = 256, crop: int = 224) -> np.ndarray:
+    """The model's Resize + CenterCrop: horizontal pass, then vertical pass, each
+    rounded half up to uint8; a pass between equal sizes is the identity."""
+    h, w = rgb.shape[:2]
+    nw, nh, left, top = resize_geometry(w, h, resize, crop)
+    a = rgb.astype(np.float64)
+    if nw != w:
+        a = _round_u8(np.einsum("ox,yxc->yoc", _bilinear_weights(w, nw), a))
+    if nh != h:
+        a = _round_u8(np.einsum("oy,yxc->oxc", _bilinear_weights(h, nh), a))
+    out = np.zeros((crop, crop, 3), np.uint8)
+    y0, y1, x0, x1 = max(top, 0), min(top + crop, nh), max(left, 0), min(left + crop, nw)
+    out[y0 - top:y1 - top, x0 - left:x1 - left] = a[y0:y1, x0:x1].astype(np.uint8)
+    return out
+
+
+# ---- the batch decoder ----------------------------------------------------------------
+
+def _pil_full(data: bytes) -> np.ndarray:
+    import io
+
+    from PIL import Image
+
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
+
+
+def _stager(device: torch.device) -> HbmStager:
+    st = _STAGERS.get(device)
+    if st is None:
+        st = _STAGERS[device] = HbmStager(device)
+    return st
+
+
+def entropy_batch(datas, threads: int = 8):
+    """The host half of ``decode_batch`` for a GPU device: the native Huffman
+    decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
+    released, so a caller may run it under the previous batch's copy and
+    kernels).  Returns what ``decode_batch(..., entropy=)`` takes."""
+    datas = [None if d is None else bytes(d) for d in datas]
+    t0 = time.perf_counter()
+    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads))
+    return datas, status, hdr, coefs, offs, time.perf_counter() - t0
+
+
+def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
+                 stager: HbmStager | None = None, entropy=None):
+    """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
+    ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
+    resized or cropped and the result is a list of [H, W, 3] tensors (``None``
+    for a ``None`` entry).  Returns ``(images, info)``; ``info["fallbacks"]``
+    lists ``(index, reason)`` of the entries ``load_image_u8`` decoded on the
+    host, ``entropy_s`` / ``h2d_s`` / ``idct_s`` / ``resize_s`` / ``kernel_s``
+    the seconds of the native Huffman decode (wall), the coefficient copy and
+    the kernels (device events).  ``entropy``: the result of ``entropy_batch``
+    on the same ``datas``, when the caller ran that ahead."""
+    device = torch.device(device)
+    full = resize is None
+    n = len(datas)
+    datas = [None if d is None else bytes(d) for d in datas] if entropy is None else entropy[0]
+    info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
+            "gpu_images": 0}
+    host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
+    if device.type != "cuda":
+        # no GPU: every image through Pillow, nothing of the native path
+        info["fallbacks"] = [(i, "cpu_device") for i, d in enumerate(datas) if d is not None]
+        imgs = [None if d is None else torch.from_numpy(host(d).copy()) for d in datas]
+        if full:
+            return imgs, info
+        out = torch.zeros((n, crop, crop, 3), dtype=torch.uint8)
+        for i, t in enumerate(imgs):
+            if t is not None:
+                out[i] = t
+        return out, info
+
+    C = _C()
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    _, status, hdr, coefs, offs, info["entropy_s"] = entropy if entropy is not None else entropy_batch(datas, threads)
+    geom = None
+    if not full:
+        hv = hdr.numpy().view(np.int32)           # JpegHeader starts with int W, H
+        seen: dict = {}                           # datasets repeat a few sizes: one evaluation per size
+        rows = [(0, 0, 0, 0)] * n
+        for i in range(n):
+            if status[i] == 0:
+                wh = (int(hv[i, 0]), int(hv[i, 1]))
+                g = seen.get(wh)
+                if g is None:
+                    g = seen[wh] = resize_geometry(wh[0], wh[1], resize, crop)
+                rows[i] = g
+        geom = torch.tensor(rows, dtype=torch.int64).view(n, 4)
+    with torch.cuda.device(device):
+        cur = torch.cuda.current_stream(device)
+        plan = C.jpeg_plan(hdr, status, offs, coefs.numel(), geom, 0 if full else int(crop), device)
+        out = torch.zeros(max(plan.out_bytes, 0) if full else n * crop * crop * 3, dtype=torch.uint8, device=device)
+        if plan.n_gpu:
+            stager = stager or _stager(device)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            ev[0].record(stager.stream)
+            dev_coefs, done = stager._stage(coefs.numpy(), (coefs.numel() * 2,))
+            ev[1].record(stager.stream)
+            cur.wait_event(done)
+            dev_coefs.record_stream(cur)
+            planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=device)
+            ev[2].record(cur)
+            C.jpeg_idct(plan, dev_coefs.view(torch.int16), planes)
+            ev[3].record(cur)
+            C.jpeg_resize_crop(plan, planes, out)
+            ev[4].record(cur)
+            ev[4].synchronize()
+            info["h2d_s"] = ev[0].elapsed_time(ev[1]) * 1e-3
+            info["idct_s"] = ev[2].elapsed_time(ev[3]) * 1e-3
+            info["resize_s"] = ev[3].elapsed_time(ev[4]) * 1e-3
+            info["kernel_s"] = info["idct_s"] + info["resize_s"]
+            info["gpu_images"] = int(plan.n_gpu)
+        imgs = []
+        if not full:
+            out = out.view(n, crop, crop, 3)
+        for i, d in enumerate(datas):
+            if d is None:
+                imgs.append(None)
+                continue
+            if status[i] != 0:
+                st, reason, _ = C.jpeg_parse(d)
+                info["fallbacks"].append((i, reason if st != 0 else "corrupt"))
+                t = torch.from_numpy(host(d).copy()).to(device)
+                if full:
+                    imgs.append(t)
+                else:
+                    out[i].copy_(t)
+            elif full:
+                h, w = int(hdr[i].numpy().view(np.int32)[1]), int(hdr[i].numpy().view(np.int32)[0])
+                o = plan.out_off[i]
+                imgs.append(out[o:o + h * w * 3].view(h, w, 3))
+        # the result is complete when it is returned, whatever the batch held (the zero fill and
+        # the fallbacks' copies too): a holder may hand it to a consumer on any other stream
+        cur.synchronize()
+    return (imgs if full else out), info

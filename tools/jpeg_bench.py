@@ -1,0 +1,140 @@
+"""JPEG source throughput: Pillow on Python threads against the native entropy
+decoder + HIP kernels.
+
+Generates N (default 2000) Pillow-encoded 500x375 images (4:2:0, quality 90,
+seeded) in a temporary directory and, in one process, after a warm-up,
+alternating three times, reports images/s of
+
+  * ``JpegSource.get``     8 workers (decode + resize in Pillow, one copy to HBM),
+  * ``GpuJpegSource.get``  cold, 8 entropy threads (nothing resident),
+  * ``GpuJpegSource.get``  warm (everything resident),
+
+and the cold path's split into entropy decode (host wall time), H2D and the two
+kernels (device events).  Needs a GPU: without one it exits with an error.
+
+    python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def make_images(d: str, n: int, seed: int = 0) -> int:
+    """Smooth structure plus noise: files of a photograph's size (~40-60 KB), not of flat colour."""
+    from PIL import Image
+
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:375, 0:500]
+    total = 0
+    for i in range(n):
+        ph = rng.uniform(0, 6.28, 6)
+        fx, fy = rng.uniform(8, 60, 3), rng.uniform(8, 60, 3)
+        a = np.stack([127.5 + 90 * np.sin(xx / fx[c] + ph[c]) * np.cos(yy / fy[c] + ph[3 + c]) for c in range(3)], 2)
+        a = np.clip(a + rng.normal(0, 12, a.shape), 0, 255).astype(np.uint8)
+        p = os.path.join(d, f"test_{i}.JPEG")
+        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2)
+        total += os.path.getsize(p)
+    return total
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--images", type=int, default=2000)
+    ap.add_argument("--threads", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    a = ap.parse_args(argv)
+
+    import torch
+
+    if not torch.cuda.is_available():
+        print("jpeg_bench: no GPU: this tool measures the GPU decode path and has no fallback", file=sys.stderr)
+        return 2
+    from idunno import ops
+    from idunno.runtime.data import GpuJpegSource, JpegSource
+
+    ops.load()
+    dev = torch.device("cuda", 0)
+    lines = []
+
+    def say(s: str) -> None:
+        print(s, flush=True)
+        lines.append(s)
+
+    n = a.images
+    with tempfile.TemporaryDirectory() as d, torch.cuda.device(dev):
+        t0 = time.perf_counter()
+        nbytes = make_images(d, n)
+        say(f"{n} images 500x375 4:2:0 q90, {nbytes / n / 1024:.1f} KiB each, generated in {time.perf_counter() - t0:.1f} s; "
+            f"{torch.cuda.get_device_name(0)}; {a.threads} threads")
+        pil = JpegSource(dev, root=d, workers=a.threads)
+
+        def timed(f):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            x = f()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t, x
+
+        # warm-up: page cache, code objects, pinned buffers, thread pools
+        w = min(n, 64)
+        timed(lambda: pil.get(0, w - 1))
+        timed(lambda: GpuJpegSource(dev, root=d, threads=a.threads).get(0, w - 1))
+        rates = {"pil": [], "cold": [], "warm": []}
+        split = {"entropy_s": [], "h2d_s": [], "idct_s": [], "resize_s": []}
+        ref = None
+        for r in range(a.reps):
+            dt, x = timed(lambda: pil.get(0, n - 1))
+            rates["pil"].append(n / dt)
+            gpu = GpuJpegSource(dev, root=d, threads=a.threads)
+            dt, y = timed(lambda: gpu.get(0, n - 1))
+            rates["cold"].append(n / dt)
+            for k in split:
+                split[k].append(gpu.seconds[k])
+            assert gpu.decoded == n and gpu.fallbacks == 0
+            dt, z = timed(lambda: gpu.get(0, n - 1))
+            rates["warm"].append(n / dt)
+            assert gpu.decoded == n and torch.equal(y, z)
+            if ref is None:
+                diff = (x.int() - y.int()).abs()
+                ref = (int(diff.max()), float(diff.float().mean()))
+            say(f"rep {r}: JpegSource {rates['pil'][-1]:9.1f} img/s | GpuJpegSource cold {rates['cold'][-1]:9.1f} img/s | "
+                f"warm {rates['warm'][-1]:12.1f} img/s")
+            del x, y, z, gpu
+        say(f"GPU output vs Pillow output over {n} images: max |diff| {ref[0]}, mean {ref[1]:.4f}")
+        for k, name in (("pil", "JpegSource.get (Pillow, threads)"), ("cold", "GpuJpegSource.get cold"),
+                        ("warm", "GpuJpegSource.get warm")):
+            v = rates[k]
+            say(f"{name:34s} median {np.median(v):12.1f} img/s  min {min(v):12.1f}  max {max(v):12.1f}  "
+                f"spread {100 * (max(v) - min(v)) / np.median(v):.1f} %")
+        say(f"cold / Pillow = {np.median(rates['cold']) / np.median(rates['pil']):.2f}x (medians)")
+        for k, name in (("entropy_s", "entropy decode (host, wall)"), ("h2d_s", "H2D of coefficients (events)"),
+                        ("idct_s", "jpeg_idct_kernel (events)"), ("resize_s", "jpeg_resize_crop_kernel (events)")):
+            v = split[k]
+            say(f"  cold split: {name:34s} median {1e3 * np.median(v):9.2f} ms  ({1e6 * np.median(v) / n:8.2f} us/image)")
+        # bytes the kernels move per image: 500x375 4:2:0 = 32x24 MCUs of 6 blocks
+        blocks = 32 * 24 * 6
+        idct_b = blocks * (128 + 64)
+        say(f"  jpeg_idct_kernel: {blocks} blocks/image, {idct_b} B/image read+written -> "
+            f"{n * idct_b / np.median(split['idct_s']) / 1e9:.1f} GB/s")
+        say(f"  jpeg_resize_crop_kernel: {224 * 224 * 3} B/image written -> "
+            f"{n * 224 * 224 * 3 / np.median(split['resize_s']) / 1e9:.2f} GB/s of output")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
