@@ -1474,24 +1474,34 @@ torch::Tensor preprocess_pack3_split(torch::Tensor img, int64_t KW, int64_t stri
   return out;
 }
 
+// Host only: (Hr, Wr, top, left) of Resize(shorter side -> resize) + CenterCrop(crop) on an
+// Hi x Wi image (tile_math.h resize_crop_geometry), the one definition resize_crop uses.
+// The offsets mean something only where the crop fits (Hr >= crop and Wr >= crop).
+std::tuple<int64_t, int64_t, int64_t, int64_t> resize_crop_geometry_py(int64_t Hi, int64_t Wi, int64_t resize,
+                                                                       int64_t crop) {
+  TORCH_CHECK(Hi >= 1 && Wi >= 1 && resize >= 1 && crop >= 1, "resize_crop_geometry: sizes must be positive");
+  TORCH_CHECK(Hi < (1 << 24) && Wi < (1 << 24) && resize < (1 << 24) && crop < (1 << 24) &&
+                  resize * std::max(Hi, Wi) / std::min(Hi, Wi) < (1 << 24),
+              "resize_crop_geometry: image too large");
+  int Hr, Wr, top, left;
+  resize_crop_geometry((int)Hi, (int)Wi, (int)resize, (int)crop, Hr, Wr, top, left);
+  return {Hr, Wr, top, left};
+}
+
 torch::Tensor resize_crop(torch::Tensor img, int64_t resize, int64_t crop) {
   CHECK_DEV(img);
   CHECK_CONTIG(img);
   CHECK_DT(img, torch::kUInt8);
   TORCH_CHECK(img.dim() == 4 && img.size(3) == 3, "img must be [B, H, W, 3] uint8");
   const int B = img.size(0), Hi = img.size(1), Wi = img.size(2);
-  int Hr, Wr;
-  if (Hi <= Wi) {
-    Hr = resize;
-    Wr = (int)((long)resize * Wi / Hi);
-  } else {
-    Wr = resize;
-    Hr = (int)((long)resize * Hi / Wi);
-  }
-  TORCH_CHECK(Hr >= crop && Wr >= crop, "crop larger than resized image");
+  TORCH_CHECK(B == 0 || (Hi >= 1 && Wi >= 1), "empty image");
   auto out = torch::empty({B, crop, crop, 4}, img.options().dtype(torch::kHalf));
-  if (B) resize_crop_launch(img.data_ptr<uint8_t>(), reinterpret_cast<half_t*>(out.data_ptr()), B, Hi, Wi, Hr, Wr,
-                            crop, cur_stream()); check_launch("resize_crop");
+  if (!B) return out;
+  const auto [Hr, Wr, top, left] = resize_crop_geometry_py(Hi, Wi, resize, crop);
+  TORCH_CHECK(Hr >= crop && Wr >= crop, "crop larger than resized image");
+  resize_crop_launch(img.data_ptr<uint8_t>(), reinterpret_cast<half_t*>(out.data_ptr()), B, Hi, Wi, (int)Hr, (int)Wr,
+                     crop, (int)top, (int)left, cur_stream());
+  check_launch("resize_crop");
   return out;
 }
 
@@ -1948,6 +1958,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("img"), py::arg("w"), py::arg("bias"), py::arg("start") = py::none(), py::arg("batch") = -1,
         py::arg("start_offset") = 0, py::arg("window") = -1, py::arg("sub") = 0);
   m.def("resize_crop", &resize_crop, "bilinear resize + centre crop + normalise");
+  m.def("resize_crop_geometry", &resize_crop_geometry_py,
+        "host only: (Hr, Wr, top, left) of resize_crop on an Hi x Wi image", py::arg("Hi"), py::arg("Wi"),
+        py::arg("resize"), py::arg("crop"));
   m.def("maxpool2d_nhwc", &maxpool2d_nhwc, "NHWC max pool (into ``out`` when given)", py::arg("x"), py::arg("k"),
         py::arg("s"), py::arg("pad"), py::arg("out") = py::none());
   m.def("global_avgpool_nhwc", &global_avgpool_nhwc, "NHWC global average pool");

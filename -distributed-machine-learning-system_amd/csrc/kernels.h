@@ -215,7 +215,7 @@ void stem_fused_launch(const uint8_t* img, const half_t* w, const float* bias, h
 void preprocess_launch(const uint8_t* img, half_t* out, long npix, const long long* start_idx,
                        long long start_off, long long max_start, long long sub, long pix_per_img, hipStream_t st);
 void resize_crop_launch(const uint8_t* img, half_t* out, int B, int Hi, int Wi, int Hr, int Wr,
-                        int crop, hipStream_t st);
+                        int crop, int top, int left, hipStream_t st);
 void maxpool_launch(const half_t* x, half_t* y, int B, int H, int W, int C, int Ho, int Wo, int k,
                     int s, int pad, hipStream_t st);
 void avgpool_launch(const half_t* x, half_t* y, int B, int HW, int C, hipStream_t st);

@@ -79,16 +79,16 @@ void preprocess_launch(const uint8_t* img, half_t* out, long npix, const long lo
 
 // Bilinear resize of an (Hi x Wi) uint8 HWC image so that its shorter side is
 // `rs`, then a centre crop of `crop` x `crop`, then normalisation.  Matches
-// torchvision's Resize (bilinear, half-pixel centres, no antialias) + CenterCrop.
+// torchvision's Resize (bilinear, half-pixel centres, no antialias) + CenterCrop;
+// (Hr, Wr, top, left) come from the host's resize_crop_geometry (tile_math.h).
 __global__ void resize_crop_kernel(const uint8_t* __restrict__ img, half_t* __restrict__ out,
-                                   int B, int Hi, int Wi, int Hr, int Wr, int crop) {
+                                   int B, int Hi, int Wi, int Hr, int Wr, int crop, int top, int left) {
   const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long npix = (long)B * crop * crop;
   if (p >= npix) return;
   const int b = (int)(p / (crop * crop));
   const int r = (int)(p - (long)b * crop * crop);
   const int oy = r / crop, ox = r - oy * crop;
-  const int top = (Hr - crop + 1) / 2, left = (Wr - crop + 1) / 2;  // round((H-c)/2)
   const int y = oy + top, x = ox + left;
   const float sy = (float)Hi / (float)Hr, sx = (float)Wi / (float)Wr;
   float fy = ((float)y + 0.5f) * sy - 0.5f, fx = ((float)x + 0.5f) * sx - 0.5f;
@@ -113,11 +113,11 @@ __global__ void resize_crop_kernel(const uint8_t* __restrict__ img, half_t* __re
 }
 
 void resize_crop_launch(const uint8_t* img, half_t* out, int B, int Hi, int Wi, int Hr, int Wr,
-                        int crop, hipStream_t st) {
+                        int crop, int top, int left, hipStream_t st) {
   const long npix = (long)B * crop * crop;
   const int bs = 256;
   hipLaunchKernelGGL(resize_crop_kernel, dim3((unsigned)((npix + bs - 1) / bs)), dim3(bs), 0, st,
-                     img, out, B, Hi, Wi, Hr, Wr, crop);
+                     img, out, B, Hi, Wi, Hr, Wr, crop, top, left);
 }
 
 // NHWC max-pool; C % 8 == 0.  One thread = 8 channels of one output pixel.
@@ -135,7 +135,7 @@ __global__ void maxpool_kernel(const half_t* __restrict__ x, half_t* __restrict_
   const int b = (int)(pix / Ho);
   half8v m;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) m[i] = (half_t)(-65504.f);
+  for (int i = 0; i < 8; ++i) m[i] = (half_t)(-INFINITY);   // as the f32 and split pools
   const int ih0 = oh * s - pad, iw0 = ow * s - pad;
   for (int dy = 0; dy < k; ++dy) {
     const int ih = ih0 + dy;
@@ -161,19 +161,20 @@ void maxpool_launch(const half_t* x, half_t* y, int B, int H, int W, int C, int 
 
 // NHWC global average pool -> [B][C] fp16.  One 256-thread workgroup per image:
 // thread (g, c8) sums pixels g, g+G, ... of 8-channel chunk c8 (16-byte loads),
-// the G partial sums meet in LDS.  (One thread per chunk over all HW pixels ran
-// 400 workgroups' worth of work on 100 workgroups with a 49-long dependent
-// chain: 17 us for the 20 MB ResNet18 layer4 output.)
+// the G partial sums meet in LDS.  The thread map is tile_math.h avgpool_map,
+// which csrc/tests/host_checks.cpp walks for every C.  (One thread per chunk over
+// all HW pixels ran 400 workgroups' worth of work on 100 workgroups with a 49-long
+// dependent chain: 17 us for the 20 MB ResNet18 layer4 output.)
 __global__ void __launch_bounds__(256) avgpool_kernel(const half_t* __restrict__ x, half_t* __restrict__ y,
                                                       int B, int HW, int C) {
   __shared__ float part[256 * 8];
   const int b = blockIdx.x;
   const int cv = C / 8;
-  const int G = cv >= 256 ? 1 : 256 / cv;          // pixel groups per chunk
+  const AvgpoolMap tm = avgpool_map(threadIdx.x, cv);
+  const int G = tm.G, g = tm.g;                    // pixel groups per chunk, this thread's group
   const half_t* p = x + (size_t)b * HW * C;
   const float inv = 1.f / (float)HW;
-  for (int c8 = threadIdx.x % cv; c8 < cv; c8 += (cv >= 256 ? 256 : cv)) {
-    const int g = cv >= 256 ? 0 : threadIdx.x / cv;
+  for (int c8 = tm.c8; c8 < cv; c8 += tm.stride) {
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (g < G) {
       for (int i = g; i < HW; i += G) {

@@ -7,7 +7,10 @@
 //     maps each XCD's round-robin share onto one contiguous logical range;
 //   * every LDS swizzle permutes the 16-byte chunks of a row, and every
 //     ds_read_b128 lane group of a 16x16x32 fragment read touches 16 distinct
-//     16-byte bank slots (MI355X_MICROARCH.md §LDS).
+//     16-byte bank slots (MI355X_MICROARCH.md §LDS);
+//   * the fp16 average pool's thread map stores every chunk once and sums every
+//     (pixel, chunk) once, for C = 8 .. 4800;
+//   * resize_crop's crop offset rounds half to even.
 // Build + run: tests/test_host_checks.py.  Exit status = number of failures.
 #include <cstdio>
 #include <vector>
@@ -114,7 +117,74 @@ static void check_wino_raw() {
   }
 }
 
+// avgpool_kernel (fp16) walked on the host with its own avgpool_map: for every
+// chunk count cv = C / 8 and pixel count HW, each chunk 0..cv-1 is stored by exactly
+// one thread, and each (pixel, chunk) is accumulated exactly once among the threads
+// that feed that store (the storing thread itself when G == 1, the G LDS partials of
+// the chunk otherwise).  A second "group" that owns no pixels but stores anyway
+// (t / cv == 1 while 256 / cv == 1) shows up as a chunk stored twice.
+static void check_avgpool_map() {
+  for (int cv = 1; cv <= 600; ++cv)
+    for (int HW : {1, 7, 49}) {
+      std::vector<int> stores(cv, 0);              // stores per chunk
+      std::vector<int> fed(cv * HW, 0);            // (chunk, pixel) sums that reach a store
+      std::vector<int> slot(256 * 8, 0);           // LDS partial (g * cv + c8) writers, in chunks of 8 floats
+      int bad_range = 0, bad_lds = 0;
+      for (int t = 0; t < 256; ++t) {
+        const AvgpoolMap m = avgpool_map(t, cv);
+        if (m.G < 1 || m.g < 0 || m.c8 < 0 || m.stride < 1) {
+          bad_range++;
+          continue;
+        }
+        for (int c8 = m.c8; c8 < cv; c8 += m.stride) {
+          const bool sums = m.g < m.G;
+          if (m.G == 1) {                          // sums (or not) and stores unconditionally
+            stores[c8]++;
+            if (sums)
+              for (int i = m.g; i < HW; i += m.G) fed[c8 * HW + i]++;
+            continue;
+          }
+          if (sums) {
+            const int s = m.g * cv + c8;
+            if (s < 0 || s >= 256) {
+              bad_lds++;
+            } else {
+              slot[s]++;
+              for (int i = m.g; i < HW; i += m.G) fed[c8 * HW + i]++;
+            }
+          }
+          if (m.g == 0) {                          // combines partials 1..G-1 of c8 and stores
+            stores[c8]++;
+            if ((m.G - 1) * cv + c8 >= 256) bad_lds++;
+          }
+          break;                                   // G > 1: one pass
+        }
+      }
+      CHECK(bad_range == 0, "avgpool cv %d: %d threads with a map out of range\n", cv, bad_range);
+      CHECK(bad_lds == 0, "avgpool cv %d: %d LDS partials outside the 256 slots\n", cv, bad_lds);
+      int once = 0, sum_once = 0, slot_once = 1;
+      for (int c = 0; c < cv; ++c) once += stores[c] == 1;
+      for (int e = 0; e < cv * HW; ++e) sum_once += fed[e] == 1;
+      for (int s = 0; s < 256; ++s) slot_once &= slot[s] <= 1;
+      CHECK(once == cv, "avgpool cv %d HW %d: %d of %d chunks stored exactly once\n", cv, HW, once, cv);
+      CHECK(sum_once == cv * HW, "avgpool cv %d HW %d: %d of %d (pixel, chunk) pairs summed exactly once\n", cv, HW,
+            sum_once, cv * HW);
+      CHECK(slot_once, "avgpool cv %d HW %d: an LDS partial has two writers\n", cv, HW);
+    }
+}
+
+// resize_crop's centre-crop offset = Python's round((n - crop) / 2.0) (half to even)
+static void check_crop_offset() {
+  for (int d = 0; d <= 4000; ++d) {
+    const int want = d % 2 == 0 ? d / 2 : (d % 4 == 1 ? (d - 1) / 2 : (d + 1) / 2);
+    CHECK(center_crop_offset(d + 224, 224) == want, "center_crop_offset: d %d -> %d, want %d\n", d,
+          center_crop_offset(d + 224, 224), want);
+  }
+}
+
 int main() {
+  check_avgpool_map();
+  check_crop_offset();
   check_groups_partition();
   check_xcd_remap();
   check_swizzle("conv_glds swz_r", 8, [](int r) { return swz_r(r, 8); });

@@ -1,6 +1,7 @@
 // Index math shared by the conv kernels and the host-side checker
 // (csrc/tests/host_checks.cpp, built with host ASan + UBSan): block-id remaps and
-// the LDS XOR swizzles.  __host__ __device__ so the checker exercises the exact
+// the LDS XOR swizzles, the fp16 average pool's thread map and the resize + crop
+// geometry.  __host__ __device__ so the checker exercises the exact
 // functions the kernels inline, not a re-typed mirror.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,5 +34,42 @@ __host__ __device__ __forceinline__ int wino_raw_swz(int p) { return ((p >> 2) &
 
 // conv3x3_c64: 128-byte rows (64 channels)
 __host__ __device__ __forceinline__ int c64_swz(int row) { return row & 6; }
+
+// avgpool_kernel (fp16): what thread t of the 256-thread workgroup does for an
+// image of cv = C / 8 eight-channel chunks.  It sums pixels g, g + G, ... of
+// chunks c8, c8 + stride, ... (< cv); a thread with g >= G idles.  G == 1: the
+// thread stores its own chunks.  G > 1 (cv <= 128, one chunk per thread): the G
+// partial sums of a chunk meet in LDS and thread g == 0 stores.  cv in (128, 256)
+// has room for one group only, so it takes the strided one-group map like
+// cv >= 256 (t / cv would put threads cv..255 in a second "group" that owns no
+// pixels but still stores).
+struct AvgpoolMap {
+  int G, g, c8, stride;
+};
+__host__ __device__ __forceinline__ AvgpoolMap avgpool_map(int t, int cv) {
+  if (cv > 128) return {1, 0, t, 256};
+  return {256 / cv, t / cv, t % cv, cv};
+}
+
+// resize_crop: torchvision's Resize(shorter side -> resize) + CenterCrop(crop)
+// geometry.  The crop offset is round-half-even of (n - crop) / 2 on integers
+// (Python's round(), as CenterCrop, load_image_u8 and the JPEG path compute it);
+// n >= crop.
+__host__ __device__ __forceinline__ int center_crop_offset(int n, int crop) {
+  const int d = n - crop, h = d / 2;
+  return (d & 1) ? h + (h & 1) : h;
+}
+__host__ __device__ __forceinline__ void resize_crop_geometry(int Hi, int Wi, int resize, int crop, int& Hr,
+                                                              int& Wr, int& top, int& left) {
+  if (Hi <= Wi) {
+    Hr = resize;
+    Wr = (int)((long)resize * Wi / Hi);
+  } else {
+    Wr = resize;
+    Hr = (int)((long)resize * Hi / Wi);
+  }
+  top = center_crop_offset(Hr, crop);
+  left = center_crop_offset(Wr, crop);
+}
 
 }  // namespace idunno

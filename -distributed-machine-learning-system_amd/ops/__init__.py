@@ -10,7 +10,7 @@ from __future__ import annotations
 from ._ext import available, load, so_path
 
 __all__ = [
-    "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop",
+    "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
@@ -253,6 +253,13 @@ def preprocess(img_u8, start=None, batch: int = -1, start_offset: int = 0, windo
 def resize_crop(img_u8, resize: int = 256, crop: int = 224):
     """Resize(shorter side) + CenterCrop + normalise, fused."""
     return load().resize_crop(img_u8, resize, crop)
+
+
+def resize_crop_geometry(hi: int, wi: int, resize: int = 256, crop: int = 224):
+    """(Hr, Wr, top, left) that ``resize_crop`` uses for an ``hi`` x ``wi`` image:
+    the resized size and the centre crop's offsets (round half to even, as
+    torchvision's CenterCrop).  Host only, needs no GPU."""
+    return tuple(int(v) for v in load().resize_crop_geometry(int(hi), int(wi), int(resize), int(crop)))
 
 
 def stem_fused(img_u8, w, bias, start=None, batch: int = -1, start_offset: int = 0, window: int = -1,

@@ -1,7 +1,9 @@
 """Native host-side checks under AddressSanitizer + UndefinedBehaviorSanitizer
 (SURVEY.md §5.2): csrc/tests/host_checks.cpp exercises the kernels' own
 __host__ __device__ index math (csrc/tile_math.h: XCD remap bijectivity, LDS
-swizzle permutations and bank-conflict freedom).  Host code only: GPU sanitizers
+swizzle permutations and bank-conflict freedom, the fp16 average pool's thread
+map storing and summing everything exactly once, resize_crop's round-half-even
+crop offset).  Host code only: GPU sanitizers
 are not available on the GPU pool."""
 import os
 import shutil
