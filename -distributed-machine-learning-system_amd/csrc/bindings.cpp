@@ -711,6 +711,73 @@ torch::Tensor conv2d_split_dual(torch::Tensor x, torch::Tensor w, torch::Tensor 
                            c10::nullopt, nsplit, center_only, acc_scale2, 1, 0);
 }
 
+// A residual block's second 3x3/s1/p1 conv with its 1x1 pad-0 downsample as a K
+// tail (conv_glds.hip TAIL): out = act(acc_scale * (conv3x3(y, W2) + conv1x1/stride2(x2, Wd)) + bias)
+// as ONE GEMM over K = [9 taps of y | channels of x2 at the strided pixel].
+//   y  : [B, Ho, Wo, 2C] split     x2 : [B, H2, W2, 2Cx] split, Ho == (H2 - 1) / stride2 + 1 (same for W)
+//   w  : [Cout, 9*2C + 2Cx] split, one exponent (models/packed.py pack_split_weight of both parts)
+// Not the fuse_down / conv2d_split_dual path above, which fuses the downsample into
+// the block's FIRST conv and still writes and re-reads the identity.
+torch::Tensor conv2d_split_tail(torch::Tensor y, torch::Tensor x2, torch::Tensor w, torch::Tensor bias,
+                                double acc_scale, int64_t stride2, bool relu, int64_t tile) {
+  CHECK_DEV(y);
+  CHECK_DEV(x2);
+  CHECK_DEV(w);
+  CHECK_DEV(bias);
+  CHECK_CONTIG(w);
+  CHECK_CONTIG(bias);
+  CHECK_DT(y, torch::kHalf);
+  CHECK_DT(x2, torch::kHalf);
+  CHECK_DT(w, torch::kHalf);
+  CHECK_DT(bias, torch::kFloat);
+  const int64_t yP = nhwc_pixel_stride(y, "y"), xP = nhwc_pixel_stride(x2, "x2");
+  TORCH_CHECK(w.dim() == 2 && bias.dim() == 1, "bad ranks");
+  TORCH_CHECK(x2.device() == y.device() && w.device() == y.device() && bias.device() == y.device(),
+              "operands on different devices");
+  const int B = y.size(0), Ho = y.size(1), Wo = y.size(2), C2 = y.size(3);
+  const int H2 = x2.size(1), W2 = x2.size(2), Cx2 = x2.size(3), Cout = w.size(0);
+  TORCH_CHECK(C2 % 64 == 0 && Cx2 % 64 == 0 && Cx2 > 0, "split operands need 2C halfs with C % 32 == 0");
+  TORCH_CHECK(w.size(1) == 9 * (int64_t)C2 + Cx2, "tail weight must be [Cout, 9*2C + 2Cx]");
+  TORCH_CHECK(bias.size(0) == Cout && Cout % 32 == 0, "bias/Cout mismatch, or Cout % 32 != 0");
+  TORCH_CHECK(stride2 >= 1 && x2.size(0) == B && Ho == (H2 - 1) / stride2 + 1 && Wo == (W2 - 1) / stride2 + 1,
+              "x2 geometry does not give y's [B, Ho, Wo] at this stride");
+  const long M = (long)B * Ho * Wo;
+  TORCH_CHECK(M * yP < (1L << 31) && (long)B * H2 * W2 * xP < (1L << 31) && M * 2 * Cout < (1L << 31),
+              "tensor too large for int32 indexing");
+  auto out = torch::empty({B, Ho, Wo, 2 * (int64_t)Cout}, y.options());
+  if (M == 0) return out;
+  ConvArgs a{};
+  a.x = reinterpret_cast<const half_t*>(y.data_ptr());
+  a.w = reinterpret_cast<const half_t*>(w.data_ptr());
+  a.bias = bias.data_ptr<float>();
+  a.y = out.data_ptr();
+  a.B = B; a.H = Ho; a.W = Wo; a.C = C2;
+  a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.ldy = 2 * Cout;
+  a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1;
+  a.M = (int)M;
+  a.Kpad = (int)w.size(1);
+  a.relu = relu ? 1 : 0;
+  a.acc_scale = (float)acc_scale;
+  a.ovf = split_guard_for(y.device());
+  a.ldx = yP != C2 ? (int)yP : 0;
+  a.zero = zero_buffer(y.device()).data_ptr();
+  a.x2 = reinterpret_cast<const half_t*>(x2.data_ptr());
+  a.H2 = H2; a.W2 = W2; a.ldx2 = (int)xP; a.stride2 = (int)stride2;
+  a.cblk2 = Cx2 / 64;
+  const int t = tile >= 0 ? (int)tile : conv_glds_split_tail_pick(a.M, Cout);
+  TORCH_CHECK(conv_glds_split_tail_launch(a, t, cur_stream()), "conv2d_split_tail: tile ", t,
+              " has no K-tail form (36 / 42)");
+  check_launch("conv_glds_split (K tail)");
+  return out;
+}
+
+// whether models/packed.py fuses a block's downsample into its second 3x3 conv by default
+// (the modes of conv_split_tail_default: 1 the rule, 2 every supported shape, 3 the rule minus the band
+// kernel's shapes)
+bool conv2d_split_tail_ok(int64_t B, int64_t Ho, int64_t Wo, int64_t C, int64_t Cx, int64_t Cout, int64_t mode) {
+  return conv_split_tail_default((int)B, (int)Ho, (int)Wo, (int)C, (int)Cx, (int)Cout, (int)mode);
+}
+
 // fp32-accurate FC on split fp16: y = act(acc_scale * x @ w.T + bias)
 //   x [M, 2K] split, w [N, 2K] split (pack_split_weight of [N, K, 1, 1]); K % 32 == 0.
 // K is cut into `splits` slices in ONE conv_glds launch (fp32 partials) + the
@@ -1894,6 +1961,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("KH"), py::arg("KW"), py::arg("stride"), py::arg("pad"),
         py::arg("relu"), py::arg("acc_scale"), py::arg("acc_scale2"), py::arg("nsplit"), py::arg("center_only"),
         py::arg("tile") = -1);
+  m.def("conv2d_split_tail", &conv2d_split_tail,
+        "split 3x3/s1/p1 conv of y + 1x1/stride2 conv of x2 as one GEMM over the concatenated K (block tail + downsample)",
+        py::arg("y"), py::arg("x2"), py::arg("w"), py::arg("bias"), py::arg("acc_scale"), py::arg("stride2"),
+        py::arg("relu"), py::arg("tile") = -1);
+  m.def("conv2d_split_tail_ok", &conv2d_split_tail_ok,
+        "whether the K-tail fusion is the default for (B, Ho, Wo, C, Cx, Cout); mode 2: wherever supported, 3: not over the band kernel",
+        py::arg("B"), py::arg("Ho"), py::arg("Wo"), py::arg("C"), py::arg("Cx"), py::arg("Cout"), py::arg("mode") = 1);
   m.def("conv2d_pack3_split", &conv2d_pack3_split, "split-fp16 RGB stem conv on packed rows, fp32 out",
         py::arg("x3"), py::arg("w"), py::arg("bias"), py::arg("W"), py::arg("KH"), py::arg("KW"), py::arg("stride"),
         py::arg("pad"), py::arg("relu"), py::arg("acc_scale"), py::arg("tile") = -1);

@@ -42,6 +42,15 @@ struct ConvArgs {
   int ldr;           // residual pixel stride in halfs (0: the output width, 2*Cout split / Cout fp16)
   int kstage;        // conv split-K (small M): block s / tiles runs K stages [s*kstage, (s+1)*kstage) of the
                      // (kh, kw, cblk) loop into fp32 partials y + s*ysplit (kslice 0); 0: off
+  // conv_glds SPLIT K tail (conv_glds_split_tail_launch): after the KH*KW*cblk stages over x, cblk2 stages
+  // over a second operand x2 = NHWC [B][H2][W2][ldx2] read at pixel (b, oh*stride2, ow*stride2), no padding;
+  // its weights follow each cout's row (Kpad = KH*KW*C + 64*cblk2).  A residual block's 3x3 conv + 1x1
+  // downsample as ONE GEMM: the identity stays in the accumulators.
+  const half_t* x2;
+  int H2, W2;
+  int ldx2;          // x2 pixel stride in halfs
+  int stride2;
+  int cblk2;         // x2 channels / 32
 };
 
 // fp32 (reference-precision) conv: same geometry fields as ConvArgs, f32 tensors.
@@ -134,6 +143,15 @@ bool conv_glds_launch(ConvArgs a, bool out_f32, int tile, hipStream_t st);
 // ([hi x32][lo x32] per 32 channels), y fp32 with out_f32
 bool conv_glds_split_launch(ConvArgs a, bool out_f32, int tile, hipStream_t st);
 int conv_glds_split_pick(int M, int Cout);
+// split 3x3-style conv over a.x with the K tail over a.x2 (ConvArgs::x2; a.cblk2 set by the caller):
+// split output, no residual, tiles 36 / 42 only (false: another tile id, or an operand past 2 GiB)
+bool conv_glds_split_tail_launch(ConvArgs a, int tile, hipStream_t st);
+int conv_glds_split_tail_pick(int M, int Cout);
+// whether a residual block's second 3x3 conv (C -> Cout on [B, Ho, Wo]) takes its 1x1 downsample (Cx
+// channels) as a K tail.  mode 1: the default rule -- supported and no split-K at this M; 2: wherever it is
+// supported (also at split-K batches: A/B arm, tests); 3: the default rule, but not where the band kernel
+// is conv2d_split's default (the "band kernel + streaming downsample" arm of the layer-2 A/B); 0: never
+bool conv_split_tail_default(int B, int Ho, int Wo, int C, int Cx, int Cout, int mode = 1);
 // K slices for a conv (1: none): force < 0 auto (the default tile), 0 / 1 off, k > 1 k slices (split-K tiles 27 / 36 / 42)
 int conv_split_ksplit(int M, int Cout, int tile, int nk_total, int force, bool legacy = false);
 bool conv1x1_small_m(long M);

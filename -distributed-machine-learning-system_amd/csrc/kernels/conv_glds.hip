@@ -62,12 +62,21 @@ __device__ __forceinline__ void wait_stages(int pending_stages) {
 // KS: conv split-K (small M) -- block s / tiles runs its own contiguous run of
 // a.kstage K stages into fp32 partials; without it the prologue has no
 // kstage / mid-tap start code (the B = 400 launches compile the plain loop).
+//
+// TAIL: a second-operand K tail (ConvArgs::x2) -- after the KH*KW*cblk stages
+// over x the loop runs cblk2 more stages whose pixels come from x2 at (b,
+// oh*stride2, ow*stride2) and whose weights simply follow in each cout's row.
+// conv3x3(y, W2) + conv1x1/s(x, Wd) of a ResNet stride-2 basic block is then
+// ONE GEMM over the concatenated K: the identity is never written to memory,
+// re-read or rounded.  Only the issue side knows; the compute side sees
+// ordinary stages and the epilogue is the no-residual one.
 template <int BN, int BM, int BK, int WN, int WM, int NS, bool HAS_RES, bool OUT_F32, bool P3 = false,
-          bool SPLIT = false, bool KS = false>
+          bool SPLIT = false, bool KS = false, bool TAIL = false>
 __global__ void __launch_bounds__(64 * WN * WM, (BM % 64 != 0 && WN * WM == 8) ? 4 : 1)   // 2nd: min waves per SIMD
 conv_glds_kernel(const ConvArgs a) {
   static_assert(!SPLIT || BK == 64, "split stages are 32 channels x (hi, lo)");
   static_assert(!KS || (OUT_F32 && !HAS_RES && !P3), "split-K writes fp32 partials");
+  static_assert(!TAIL || (SPLIT && !KS && !P3 && !HAS_RES && !OUT_F32), "K tail: split in, split out, no residual");
   constexpr int NW = WN * WM;
   constexpr int NT = 64 * NW;
   constexpr int TN = BN / WN, TM = BM / WM;
@@ -182,6 +191,27 @@ conv_glds_kernel(const ConvArgs a) {
     a_voff[j] = n < a.Cout ? (uint32_t)((n * a.Kpad + a_ch[j]) * 2) : OOR;
   }
   auto set_tap = [&]() {
+    if constexpr (TAIL) {
+      // the tail's offsets, recomputed from m at the switch (once per tile) instead of
+      // a second offset set held across the 3x3 stages: the tiles sit at their VGPR caps
+      if (i_kh == a.KH) {
+#pragma unroll
+        for (int j = 0; j < GB; ++j) {
+          const int row = (wave + NW * j) * RPI + lrow;
+          const int m = m0 + row;
+          uint32_t v = OOR;
+          if (row < BM && m < a.M) {
+            const int hw = a.Ho * a.Wo;
+            const int b = m / hw, r = m - b * hw;
+            const int oh = r / a.Wo, ow = r - oh * a.Wo;
+            const int pix = (b * a.H2 + oh * a.stride2) * a.W2 + ow * a.stride2;
+            v = (uint32_t)((pix * a.ldx2 + (lslot ^ swz_r(row, CPR)) * 8) * 2);
+          }
+          b_voff[j] = v;
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < GB; ++j) {
       const int ih = b_ih0[j] + i_kh, iw = b_iw0[j] + i_kw;
@@ -196,6 +226,13 @@ conv_glds_kernel(const ConvArgs a) {
     char* base = smem + buf * STAGE;
     if (i_cb == 0) set_tap();
     const int koff = i_s * BK * 2, coff = i_cb * BK * 2;
+    // TAIL: the tail's stages read x2 through a resource of its own (wave-uniform select)
+    const auto b_rsrc = [&] {
+      if constexpr (TAIL)
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(i_kh == a.KH ? a.x2 : xin), 0, 0x7fffffff, 0x00020000);
+      else
+        return x_rsrc;
+    }();
 #pragma unroll
     for (int j = 0; j < GA; ++j)
       dma_buf16(w_rsrc, base + (wave + NW * j) * 1024, a_voff[j], koff);
@@ -207,10 +244,10 @@ conv_glds_kernel(const ConvArgs a) {
         static_assert(BMD == BM || (NS == 2 && BM % RPI == 0), "skipped padding instructions need vmcnt(0) waits");
         if ((wave + NW * j) * RPI >= BM) continue;
       }
-      dma_buf16(x_rsrc, base + A_BYTES + (wave + NW * j) * 1024, b_voff[j], coff);
+      dma_buf16(b_rsrc, base + A_BYTES + (wave + NW * j) * 1024, b_voff[j], coff);
     }
     ++i_s;
-    if (++i_cb == a.cblk) {
+    if (++i_cb == (TAIL && i_kh == a.KH ? a.cblk2 : a.cblk)) {
       i_cb = 0;
       if (++i_kw == a.KW) {
         i_kw = 0;
@@ -530,11 +567,12 @@ conv_glds_kernel(const ConvArgs a) {
 // the buffer-resource DMA addresses x and w with 32-bit byte offsets
 static bool glds_fits(const ConvArgs& a) {
   const long xb = (long)a.B * a.H * a.W * (a.ldx ? a.ldx : a.C) * 2, wb = (long)a.Cout * a.Kpad * 2;
-  return xb < (1L << 31) && wb < (1L << 31);
+  const long x2b = a.x2 ? (long)a.B * a.H2 * a.W2 * a.ldx2 * 2 : 0;
+  return xb < (1L << 31) && wb < (1L << 31) && x2b < (1L << 31);
 }
 
 template <int BN, int BM, int BK, int WN, int WM, int NS, bool HAS_RES, bool OUT_F32, bool P3 = false,
-          bool SPLIT = false, bool KS = false>
+          bool SPLIT = false, bool KS = false, bool TAIL = false>
 static void glds_cfg(ConvArgs a, hipStream_t st) {
   a.tiles_n = (a.Cout + BN - 1) / BN;
   a.tiles_m = (a.M + BM - 1) / BM;
@@ -544,13 +582,13 @@ static void glds_cfg(ConvArgs a, hipStream_t st) {
     a.nK = (a.KH * a.cpk + cps - 1) / cps;
   } else {
     a.cblk = a.C / BK;
-    a.nK = a.KH * a.KW * a.cblk;
+    a.nK = a.KH * a.KW * a.cblk + (TAIL ? a.cblk2 : 0);
   }
   const int grid = a.tiles_n * a.tiles_m * (a.ksplit > 1 ? a.ksplit : 1);
   constexpr int RPI_ = 64 / (BK / 8), NW_ = WN * WM;
   constexpr int BMD = (BM + RPI_ * NW_ - 1) / (RPI_ * NW_) * (RPI_ * NW_);
   const size_t lds = (size_t)NS * (BN + BMD) * BK * 2;
-  auto kern = conv_glds_kernel<BN, BM, BK, WN, WM, NS, HAS_RES, OUT_F32, P3, SPLIT, KS>;
+  auto kern = conv_glds_kernel<BN, BM, BK, WN, WM, NS, HAS_RES, OUT_F32, P3, SPLIT, KS, TAIL>;
   ensure_lds_attr(reinterpret_cast<const void*>(kern), (int)lds);   // per (kernel, device), launch_util.h
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WN * WM), lds, st, a);
 }
@@ -660,6 +698,19 @@ bool conv_glds_split_launch(ConvArgs a, bool out_f32, int tile, hipStream_t st) 
   return out_f32 ? glds_dispatch_split<false, true>(a, tile, st) : glds_dispatch_split<false, false>(a, tile, st);
 }
 
+// K-tail instantiations: the two tiles conv_glds_split_pick gives the ResNet
+// layer-3 / layer-4 residual convs (split output, no residual: the identity is
+// in the accumulators)
+bool conv_glds_split_tail_launch(ConvArgs a, int tile, hipStream_t st) {
+  if (a.x2 == nullptr || a.cblk2 <= 0 || a.res != nullptr || a.kstage > 0 || a.ksplit > 1 || a.nsplit_n > 0) return false;
+  if (!glds_fits(a)) return false;
+  switch (tile) {
+    case 36: glds_cfg<128, 128, 64, 2, 4, 2, false, false, false, true, false, true>(a, st); return true;
+    case 42: glds_cfg<128, 160, 64, 4, 2, 2, false, false, false, true, false, true>(a, st); return true;
+    default: return false;
+  }
+}
+
 // Conv split-K for small M (strong scaling: a 400-image query over 8 GPUs is 50
 // images per GPU, and ResNet layer4 then makes 64 blocks of tile 42 on 256 CUs):
 // K slices of whole (kh, kw, cblk) stage runs in ONE launch into fp32 partials,
@@ -713,6 +764,31 @@ int conv_f16_ksplit(int M, int Cout, int tile, int nk_total, int force) {
 int conv_glds_split_pick(int M, int Cout) {
   if (Cout % 128 == 0) return M >= 50000 ? 36 : 42;
   return 27;
+}
+
+int conv_glds_split_tail_pick(int M, int Cout) {
+  const int t = conv_glds_split_pick(M, Cout);
+  return t == 42 ? 42 : 36;                     // Cout % 128 != 0: the 128 x 128 tile masks the missing couts
+}
+
+// The K tail as a block's default (models/packed.py fuse_down_tail): the shapes of the
+// tail instantiations' tiles, except where conv2d_split picks split-K (small M: the
+// runner keeps conv_split_ksplit + splitk_reduce_res and the separate downsample;
+// fused without split-K ResNet18 b50 is -7.4 %, profiles/r7_ab_tail_b50_forced.log).
+// Where the band kernel is the unfused default (W 28, ResNet layer2) the fused 128 x 128
+// im2col tile still wins the whole graph (+1.1 / +0.9 % over band kernel + streaming
+// downsample at B = 400, profiles/r7_ab_tail_b400_layer2.log).
+// mode 2: every supported shape; 3: the rule minus the band kernel's shapes (A/B arms).
+bool conv_split_tail_default(int B, int Ho, int Wo, int C, int Cx, int Cout, int mode) {
+  if (mode <= 0) return false;
+  if (B <= 0 || C % 32 != 0 || Cx % 32 != 0 || Cx <= 0 || Cout % 128 != 0) return false;
+  const long M = (long)B * Ho * Wo;
+  // 32-bit byte offsets (glds_fits): y / out are 4*M*C bytes, x2 at most 16*M*Cx (stride2 <= 2)
+  if (4 * M * (C > Cout ? C : Cout) >= (1L << 31) || 16 * M * Cx >= (1L << 31)) return false;
+  if (mode == 2) return true;
+  if (conv_split_ksplit((int)M, Cout, conv_glds_split_pick((int)M, Cout), 9 * (C / 32), -1) > 1) return false;
+  if (mode == 3) return !(Ho == Wo && conv3x3_band_supported(Ho, Wo, C, Cout) && conv3x3_band_default(B, Wo, Cout));
+  return true;
 }
 
 // Small-M 1x1 convs (the ResNet downsample at B = 50 per GPU: M 9800 / 2450) run on the

@@ -245,16 +245,18 @@ def from_split(xs: torch.Tensor) -> torch.Tensor:
     return (v[..., 0, :] + v[..., 1, :]).reshape(*xs.shape[:-1], c)
 
 
-def pack_split_weight(w: torch.Tensor) -> tuple[torch.Tensor, float]:
+def pack_split_weight(w: torch.Tensor, e: int | None = None) -> tuple[torch.Tensor, float]:
     """[Cout, Cin, KH, KW] -> (split weights [Cout, KH*KW*2*Cin] half, acc_scale).
 
     K order (kh, kw, 32-channel block, hi|lo, channel); the weights are scaled
     by 2^e (e from max |w|, so the largest is in [2^13, 2^14)) in fp64 before
-    the split, acc_scale = 2^-e undoes it exactly in the epilogue."""
+    the split, acc_scale = 2^-e undoes it exactly in the epilogue.  ``e``
+    forces the exponent (parts of one GEMM share one: pack_split_tail_weight)."""
     cout, cin, kh, kw = w.shape
     if cin % SPLIT_BLOCK:
         raise ValueError(f"split weights need Cin % {SPLIT_BLOCK} == 0, got {cin}")
-    e = _split_scale(w)
+    if e is None:
+        e = _split_scale(w)
     ws = w.double().permute(0, 2, 3, 1) * (2.0 ** e)
     hi = ws.half()
     lo = (ws - hi.double()).half()
@@ -266,6 +268,19 @@ def pack_split_weight(w: torch.Tensor) -> tuple[torch.Tensor, float]:
 def _split_scale(w: torch.Tensor) -> int:
     mx = float(w.abs().max())
     return 0 if mx == 0.0 else 14 - math.ceil(math.log2(mx))
+
+
+def pack_split_tail_weight(w2: torch.Tensor, wd: torch.Tensor) -> tuple[torch.Tensor, float]:
+    """Weights of ops.conv2d_split_tail: [Cout, C, 3, 3] and the 1x1 downsample
+    [Cout, Cx, 1, 1] -> ([Cout, 9*2C + 2Cx] split half, acc_scale).  Each part is
+    packed as pack_split_weight does, with ONE exponent from the max |w| over
+    both (the GEMM has one accumulator scale), the tail's K after the nine taps."""
+    if wd.shape[0] != w2.shape[0] or tuple(wd.shape[2:]) != (1, 1) or tuple(w2.shape[2:]) != (3, 3):
+        raise ValueError("tail weights: [Cout, C, 3, 3] and [Cout, Cx, 1, 1]")
+    e = _split_scale(torch.cat([w2.flatten(), wd.flatten()]))
+    s2, scale = pack_split_weight(w2, e)
+    sd, _ = pack_split_weight(wd, e)
+    return torch.cat([s2, sd], dim=1).contiguous(), scale
 
 
 def pack_split_weight_p3(w: torch.Tensor) -> tuple[torch.Tensor, float]:
@@ -607,11 +622,23 @@ class HipRunner:
         # None = measured default (_auto_batch_parts)
         self.batch_parts: int | None = None
         # split path: a stride-2 block's 1x1/2 downsample in the same launch as
-        # its 3x3/2 conv (the downsample is that conv's centre tap; one input
-        # read, one launch).  Measured slower (-2.1 / -3.1 % whole forward,
-        # profiles/r3_dual_downsample.md), so off by default
+        # its FIRST conv, the 3x3/2 (the downsample is that conv's centre tap; one
+        # input read, one launch).  The identity is still written to memory and
+        # read back as the second conv's residual.  Measured slower (-2.1 / -3.1 %
+        # whole forward, profiles/r3_dual_downsample.md), so off by default
         self.fuse_down = False
         self._dual: dict = {}
+        # split path: the downsample as a K tail of the block's SECOND 3x3 conv
+        # (ops.conv2d_split_tail: one GEMM over [9 taps of y | x at the strided
+        # pixel]) -- no downsample launch, the identity never exists in memory.
+        # A different fusion from fuse_down above.  0 / False: off (the separate
+        # downsample + residual epilogue, the launch sequence before this fusion);
+        # 1 / True: where the library's rule says so (ops.conv2d_split_tail_ok: not
+        # at split-K batches); 2: every supported block (also over split-K: tests,
+        # A/B arm); 3: the rule, but ResNet layer2 stays on the band kernel + streaming
+        # downsample (A/B arm).  ResNet18 b400 +3.2 %, b50 +1.8 % (docs/KERNELS.md)
+        self.fuse_down_tail = 1
+        self._tail: dict = {}
         # fp16 bottleneck blocks with a 1x1 downsample: the expansion 1x1 and the
         # downsample as ONE GEMM over [y | x] (ops.conv1x1_dual), so the
         # downsample's output (the residual) never reaches HBM
@@ -985,7 +1012,8 @@ class HipRunner:
         """Kernel-choice switches a captured graph depends on (part of its cache key)."""
         return (self.split, self.split_front, self.split_streams, self.winograd, self.wino_variant, self.pack3,
                 self.pack3_f16, self.side_down, self.stem_parts, self.front_split, self.fuse_stem, self.batch_parts,
-                self.fuse_down, self.fuse_down_1x1, self.fuse_next_1x1, self.stem_u8, self.route)
+                self.fuse_down, self.fuse_down_1x1, self.fuse_next_1x1, self.stem_u8, self.route,
+                int(self.fuse_down_tail))
 
     def _split_ok(self) -> bool:
         p = self.p
@@ -1049,6 +1077,11 @@ class HipRunner:
             both = self.ops.conv2d_split_dual(x, w, b, c0.s_scale, d.s_scale, c0.cout, 3, 3, c0.stride, 1, True)
             y, idt = both[..., :2 * c0.cout], both[..., 2 * c0.cout:]
             return self._conv_split(blk.convs[1], y, residual=idt, out_f32=last, out=out)
+        if not last and out is None and self._tail_ok(blk, x):
+            c0, c1, d = blk.convs[0], blk.convs[1], blk.down
+            y = self._conv_split(c0, x)
+            w, b, scale = self._tail_weights(blk)
+            return self.ops.conv2d_split_tail(y, x, w, b, scale, d.stride, c1.relu)
         if not last and out is None and self._dual1_split_ok(blk, x):
             y = x
             for c in blk.convs[:-1]:
@@ -1060,6 +1093,33 @@ class HipRunner:
         for c in blk.convs[:-1]:
             y = self._conv_split(c, y)
         return self._conv_split(blk.convs[-1], y, residual=idt, out_f32=last, out=out)
+
+    def _tail_ok(self, blk, x) -> bool:
+        """A basic block (two 3x3 convs) with a 1x1 pad-0 downsample whose shape
+        the library fuses by default (fuse_down_tail)."""
+        d = blk.down
+        if not (int(self.fuse_down_tail) and d is not None and len(blk.convs) == 2 and x.is_cuda):
+            return False
+        c0, c1 = blk.convs
+        if not (c1.kh == c1.kw == 3 and c1.stride == 1 and c1.pad == 1 and d.kh == d.kw == 1 and d.pad == 0
+                and not d.relu and d.cout == c1.cout and c1.cin == c0.cout and d.cin == c0.cin
+                and c1.sw is not None and d.sw is not None and c0.sw is not None):
+            return False
+        ho = (x.shape[1] + 2 * c0.pad - c0.kh) // c0.stride + 1
+        wo = (x.shape[2] + 2 * c0.pad - c0.kw) // c0.stride + 1
+        if ho != (x.shape[1] - 1) // d.stride + 1 or wo != (x.shape[2] - 1) // d.stride + 1:
+            return False
+        return self.ops.conv2d_split_tail_ok(x.shape[0], ho, wo, c1.cin, d.cin, c1.cout, int(self.fuse_down_tail))
+
+    def _tail_weights(self, blk):
+        """[W2 | Wd] as ONE split weight (one exponent from the max |w| over
+        both), bias = the two biases' sum; built once per block."""
+        key = id(blk)
+        if key not in self._tail:
+            c1, d = blk.convs[1], blk.down
+            sw, scale = pack_split_tail_weight(unpack_split_weight(c1).cpu(), unpack_split_weight(d).cpu())
+            self._tail[key] = (sw.to(self.device), (c1.b + d.b).contiguous(), scale)
+        return self._tail[key]
 
     def _dual1_split_ok(self, blk, x) -> bool:
         d, last = blk.down, blk.convs[-1]

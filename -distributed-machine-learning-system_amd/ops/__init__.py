@@ -13,7 +13,7 @@ __all__ = [
     "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
-    "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
+    "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
 ]
 
@@ -43,6 +43,29 @@ def conv2d_split_dual(x, w, bias, acc_scale: float, acc_scale2: float, nsplit: i
     split convs read in place)."""
     return load().conv2d_split_dual(x, w, bias, kh, kw, stride, pad, relu, acc_scale, acc_scale2, nsplit,
                                     center_only, tile)
+
+
+def conv2d_split_tail(y, x2, w, bias, acc_scale: float, stride2: int, relu: bool, tile: int = -1):
+    """A basic block's second 3x3/s1/p1 conv with the block's 1x1 pad-0
+    downsample as a K tail: act(conv3x3(y, W2) + conv1x1/stride2(x2, Wd) + bias)
+    as ONE GEMM over K = [9 taps of y | x2's channels at the strided pixel], so
+    the identity stays in the fp32 accumulators (never stored, re-read or
+    rounded).  ``w`` = [Cout, 9*2C + 2Cx] split weights with one ``acc_scale``
+    (models.packed.pack_split_tail_weight), ``bias`` the two biases' sum.
+    ``tile``: 36 (128 x 128) or 42 (128 x 160); -1 the shape's default.  Not
+    ``conv2d_split_dual``, which fuses the downsample into the FIRST conv and
+    still writes the identity."""
+    return load().conv2d_split_tail(y, x2, w, bias, acc_scale, stride2, relu, tile)
+
+
+def conv2d_split_tail_ok(b: int, ho: int, wo: int, c: int, cx: int, cout: int, mode: int = 1) -> bool:
+    """Whether ``conv2d_split_tail`` is supported AND the default for this
+    block shape (the rule lives in the library: conv_glds.hip
+    conv_split_tail_default): false where the unfused conv would take split-K
+    (small M).  ``mode`` 2: every supported shape (tests at small batches, A/B
+    arm); 3: the rule, but not where the band kernel is the unfused default
+    (W 28: the other arm of the layer-2 A/B); 0: never."""
+    return bool(load().conv2d_split_tail_ok(b, ho, wo, c, cx, cout, mode))
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,
