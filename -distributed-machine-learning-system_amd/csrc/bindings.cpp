@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "launch_util.h"
 #include "runtime/jpeg_entropy.h"
+#include "runtime/jpeg_huff_pack.h"
 
 using namespace idunno;
 
@@ -1929,6 +1930,100 @@ void jpeg_resize_crop(const std::shared_ptr<JpegPlan>& plan, torch::Tensor plane
   check_launch("jpeg_resize_crop");
 }
 
+// ---- JPEG entropy stage on the device (runtime/jpeg_huff_pack.cpp, kernels/jpeg_entropy.hip) ----
+// A parsed and packed batch, all on the host: what jpeg_entropy_batch returns minus the
+// coefficients, plus the three buffers the entropy kernel reads.
+struct JpegHuffPacked {
+  std::vector<int64_t> status;       // per entry: the header parse's verdict (the kernel's comes later)
+  std::vector<int64_t> offs;         // first coefficient of each accepted entry, else -1
+  torch::Tensor hdr;                 // uint8 [n, sizeof(JpegHeader)]
+  torch::Tensor bytes, sets, desc;   // uint8: entropy-coded bytes, JpegHuffSet[], JpegHuffDesc[n]
+  int64_t n = 0, n_gpu = 0, nsets = 0, byte_total = 0, coef_total = 0;
+};
+
+// Parses a list of bytes / None and packs the accepted entries, GIL released.
+std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas) {
+  const int n = (int)datas.size();
+  std::vector<const uint8_t*> ptr(n, nullptr);
+  std::vector<size_t> len(n, 0);
+  for (int i = 0; i < n; ++i) {
+    py::handle o = datas[i];
+    if (!o.is_none()) bytes_span(o, &ptr[i], &len[i]);
+    if (ptr[i] != nullptr && len[i] == 0) ptr[i] = nullptr;
+  }
+  auto pk = std::make_shared<JpegHuffPacked>();
+  pk->n = n;
+  pk->hdr = torch::zeros({n, (int64_t)sizeof(JpegHeader)}, torch::kUInt8);
+  std::vector<int> status(n, JPEG_EMPTY);
+  JpegHuffBatch b;
+  {
+    py::gil_scoped_release nogil;
+    jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b);
+  }
+  const char* why = jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total);
+  TORCH_CHECK(why == nullptr, "jpeg_huff_pack: bad descriptor: ", why ? why : "");
+  pk->bytes = torch::empty({b.byte_total}, torch::kUInt8);
+  pk->sets = torch::empty({(int64_t)(b.sets.size() * sizeof(JpegHuffSet))}, torch::kUInt8);
+  pk->desc = torch::empty({(int64_t)(b.desc.size() * sizeof(JpegHuffDesc))}, torch::kUInt8);
+  {
+    py::gil_scoped_release nogil;
+    if (b.byte_total) jpeg_huff_copy_bytes(b, ptr.data(), len.data(), pk->bytes.data_ptr<uint8_t>());
+    if (!b.sets.empty()) std::memcpy(pk->sets.data_ptr(), b.sets.data(), b.sets.size() * sizeof(JpegHuffSet));
+    if (!b.desc.empty()) std::memcpy(pk->desc.data_ptr(), b.desc.data(), b.desc.size() * sizeof(JpegHuffDesc));
+  }
+  pk->status.assign(status.begin(), status.end());
+  pk->offs.assign(n, -1);
+  for (int i = 0; i < n; ++i)
+    if (b.desc[i].gpu) {
+      pk->offs[i] = b.desc[i].coef_base;
+      ++pk->n_gpu;
+    }
+  pk->nsets = (int64_t)b.sets.size();
+  pk->byte_total = b.byte_total;
+  pk->coef_total = b.coef_total;
+  return pk;
+}
+
+// Zeroes coefs and decodes the packed batch into it on the current stream: bytes uint8 (the
+// packed bytes, on the device), coefs int16 [>= coef_total], status int32 [n] (written for the
+// accepted entries only).  Every descriptor is checked against these very buffers first.
+void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
+                      torch::Tensor status) {
+  TORCH_CHECK(pk != nullptr, "no packed batch");
+  if (pk->n_gpu == 0) return;
+  CHECK_DEV(bytes);
+  CHECK_DEV(coefs);
+  CHECK_DEV(status);
+  CHECK_CONTIG(bytes);
+  CHECK_CONTIG(coefs);
+  CHECK_CONTIG(status);
+  CHECK_DT(bytes, torch::kUInt8);
+  CHECK_DT(coefs, torch::kInt16);
+  CHECK_DT(status, torch::kInt32);
+  TORCH_CHECK(coefs.device() == bytes.device() && status.device() == bytes.device(), "device mismatch");
+  TORCH_CHECK(status.numel() >= pk->n && pk->n < (1ll << 31), "jpeg_entropy_gpu: status buffer too small");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bytes.data_ptr()) % 16 == 0, "jpeg_entropy_gpu: bytes must be 16-byte aligned");
+  TORCH_CHECK(pk->desc.numel() == pk->n * (int64_t)sizeof(JpegHuffDesc) &&
+                  pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet), "jpeg_entropy_gpu: packed batch changed");
+  const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
+                                    bytes.numel(), pk->nsets, coefs.numel());
+  TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
+  auto dev_desc = pk->desc.to(bytes.device());
+  auto dev_sets = pk->sets.to(bytes.device());
+  jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr()),
+                      reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), coefs.data_ptr<int16_t>(),
+                      status.data_ptr<int>(), (int)pk->n, cur_stream());
+  check_launch("jpeg_entropy");
+}
+
+void jpeg_entropy_zero(torch::Tensor coefs) {
+  CHECK_DEV(coefs);
+  CHECK_CONTIG(coefs);
+  CHECK_DT(coefs, torch::kInt16);
+  jpeg_entropy_zero_launch(coefs.data_ptr<int16_t>(), coefs.numel(), cur_stream());
+  check_launch("jpeg_entropy_zero");
+}
+
 namespace idunno {
 std::vector<double> stage_file_native(const std::string& path, torch::Tensor out, std::vector<torch::Tensor> pinned,
                                       int64_t stream, int64_t nthreads);
@@ -2064,6 +2159,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jpeg_plan", &jpeg_plan, "validate a decoded batch and build its device descriptor tables",
         py::arg("hdr"), py::arg("status"), py::arg("offs"), py::arg("coef_elems"), py::arg("geom"), py::arg("crop"),
         py::arg("device"));
+  py::class_<JpegHuffPacked, std::shared_ptr<JpegHuffPacked>>(m, "JpegHuffPacked")
+      .def_readonly("status", &JpegHuffPacked::status)
+      .def_readonly("offs", &JpegHuffPacked::offs)
+      .def_readonly("hdr", &JpegHuffPacked::hdr)
+      .def_readonly("bytes", &JpegHuffPacked::bytes)
+      .def_readonly("n", &JpegHuffPacked::n)
+      .def_readonly("n_gpu", &JpegHuffPacked::n_gpu)
+      .def_readonly("nsets", &JpegHuffPacked::nsets)
+      .def_readonly("byte_total", &JpegHuffPacked::byte_total)
+      .def_readonly("coef_total", &JpegHuffPacked::coef_total);
+  m.def("jpeg_huff_pack", &jpeg_huff_pack,
+        "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage",
+        py::arg("datas"));
+  m.def("jpeg_entropy_zero", &jpeg_entropy_zero, "async memset of a device coefficient buffer", py::arg("coefs"));
+  m.def("jpeg_entropy_gpu", &jpeg_entropy_gpu,
+        "Huffman-decode a packed batch on the device: one lane per image, int32 status per image",
+        py::arg("packed"), py::arg("bytes"), py::arg("coefs"), py::arg("status"));
   m.def("jpeg_idct", &jpeg_idct, "dequantise + 8x8 IDCT of a planned batch into uint8 component planes",
         py::arg("plan"), py::arg("coefs"), py::arg("planes"));
   m.def("jpeg_resize_crop", &jpeg_resize_crop,

@@ -278,4 +278,14 @@ void jpeg_idct_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc*
 void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,
                              hipStream_t st);
 
+// ---- JPEG entropy stage on the device (jpeg_entropy.hip, jpeg_huff_core.h) ----
+struct JpegHuffSet;
+struct JpegHuffDesc;
+// async memset of the batch coefficient buffer: the kernel writes only non-zero coefficients
+void jpeg_entropy_zero_launch(int16_t* coef, long long coef_elems, hipStream_t st);
+// one lane per entry of desc[0, n); status[i] is written for the entries with gpu == 1.  The caller
+// has run jpeg_huff_check (runtime/jpeg_huff_pack.h) over desc against the three buffers.
+void jpeg_entropy_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc, int16_t* coef,
+                         int* status, int n, hipStream_t st);
+
 }  // namespace idunno

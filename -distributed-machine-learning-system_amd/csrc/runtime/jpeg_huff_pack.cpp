@@ -1,0 +1,220 @@
+// Host packer of the device entropy stage (see jpeg_huff_pack.h).
+#include "jpeg_huff_pack.h"
+
+#include <cstring>
+#include <map>
+#include <string>
+
+namespace idunno {
+
+static_assert(kJpegHuffOk == JPEG_OK && kJpegHuffCorrupt == JPEG_CORRUPT, "core statuses are JpegStatus values");
+
+namespace {
+
+// The DHT payload of one table slot: 16 counts, then the symbols.
+struct RawTab {
+  bool defined = false;
+  uint8_t counts[16];
+  int nvals = 0;
+  uint8_t vals[256];
+};
+
+struct RawSet {
+  RawTab t[8];            // dc 0..3, ac 0..3
+  int td[3], ta[3];
+};
+
+inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
+
+// Walks the segments of a file jpeg_parse_header accepted (so every length and
+// every DHT payload has been validated) up to SOS at scan_pos; a later DHT of a
+// slot replaces an earlier one.  false: the file is not what parse saw.
+bool read_tables(const uint8_t* data, size_t n, const JpegHeader& hdr, RawSet* rs) {
+  size_t pos = 2;
+  while (pos + 2 <= n && pos < hdr.scan_pos) {
+    if (data[pos] != 0xFF) return false;
+    while (pos < n && data[pos] == 0xFF) ++pos;
+    if (pos >= n) return false;
+    const int m = data[pos++];
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+    if (pos + 2 > n) return false;
+    const size_t L = (size_t)be16(data + pos);
+    if (L < 2 || pos + L > n) return false;
+    const uint8_t* seg = data + pos + 2;
+    const size_t slen = L - 2;
+    pos += L;
+    if (m == 0xC4) {
+      size_t p = 0;
+      while (p < slen) {
+        const int tc = seg[p] >> 4, th = seg[p] & 15;
+        if (tc > 1 || th > 3 || p + 17 > slen) return false;
+        RawTab& t = rs->t[4 * tc + th];
+        int total = 0;
+        for (int l = 0; l < 16; ++l) total += seg[p + 1 + l];
+        if (total > 256 || p + 17 + (size_t)total > slen) return false;
+        std::memcpy(t.counts, seg + p + 1, 16);
+        std::memset(t.vals, 0, sizeof(t.vals));
+        std::memcpy(t.vals, seg + p + 17, (size_t)total);
+        t.nvals = total;
+        t.defined = true;
+        p += 17 + (size_t)total;
+      }
+    } else if (m == 0xDA) {
+      if (pos != hdr.scan_pos || slen != (size_t)(4 + 2 * hdr.ncomp) || seg[0] != hdr.ncomp) return false;
+      for (int c = 0; c < hdr.ncomp; ++c) {
+        rs->td[c] = seg[2 + 2 * c] >> 4;
+        rs->ta[c] = seg[2 + 2 * c] & 15;
+        if (rs->td[c] > 3 || rs->ta[c] > 3) return false;
+        if (!rs->t[rs->td[c]].defined || !rs->t[4 + rs->ta[c]].defined) return false;
+      }
+      return true;
+    }
+  }
+  return false;
+}
+
+// canonical code tables of one slot, in the core's form; false: counts no code can have
+bool build_tab(const RawTab& r, JpegHuffTab* t) {
+  std::memset(t, 0, sizeof(*t));
+  for (int l = 0; l <= 16; ++l) t->maxcode[l] = -1;
+  if (!r.defined) return true;          // holds no code: every lookup fails
+  std::memcpy(t->vals, r.vals, sizeof(t->vals));
+  t->nvals = r.nvals;
+  int32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int cnt = r.counts[l - 1];
+    if (code + cnt > (1 << l)) return false;
+    t->valptr[l] = k;
+    t->mincode[l] = code;
+    t->maxcode[l] = cnt ? code + cnt - 1 : -1;
+    if (l <= kJpegHuffLookBits) {
+      const int rep = 1 << (kJpegHuffLookBits - l);
+      for (int i = 0; i < cnt; ++i)
+        for (int j = 0; j < rep; ++j) t->look[(code + i) * rep + j] = (uint16_t)((l << 8) | r.vals[k + i]);
+    }
+    k += cnt;
+    code = (code + cnt) << 1;
+  }
+  return true;
+}
+
+std::string set_key(const RawSet& rs) {
+  std::string key;
+  for (const RawTab& t : rs.t) {
+    key.push_back(t.defined ? 1 : 0);
+    if (!t.defined) continue;
+    key.append(reinterpret_cast<const char*>(t.counts), 16);
+    key.append(reinterpret_cast<const char*>(t.vals), (size_t)t.nvals);
+  }
+  return key;
+}
+
+inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+}  // namespace
+
+void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
+                    JpegHuffBatch* out) {
+  out->desc.assign((size_t)n, JpegHuffDesc{});
+  out->sets.clear();
+  out->byte_total = out->coef_total = 0;
+  std::map<std::string, int> seen;
+  std::vector<RawSet> rsv(1);                 // ~2 KB: off the stack
+  for (int i = 0; i < n; ++i) {
+    JpegHuffDesc& d = out->desc[(size_t)i];
+    std::memset(&hdr[i], 0, sizeof(hdr[i]));
+    if (data[i] == nullptr || len[i] == 0) {
+      status[i] = JPEG_EMPTY;
+      continue;
+    }
+    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i]);
+    if (status[i] != JPEG_OK) continue;
+    const JpegHeader& h = hdr[i];
+    RawSet& rs = rsv[0];
+    rs = RawSet{};
+    if (h.scan_pos > len[i] || len[i] - h.scan_pos > 0xFFFFFFF0u || !read_tables(data[i], len[i], h, &rs)) {
+      status[i] = JPEG_CORRUPT;
+      continue;
+    }
+    const std::string key = set_key(rs);
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      JpegHuffSet s;
+      bool ok = true;
+      for (int t = 0; t < 4; ++t) ok = ok && build_tab(rs.t[t], &s.dc[t]) && build_tab(rs.t[4 + t], &s.ac[t]);
+      if (!ok) {
+        status[i] = JPEG_CORRUPT;
+        continue;
+      }
+      it = seen.emplace(key, (int)out->sets.size()).first;
+      out->sets.push_back(s);
+    }
+    d.gpu = 1;
+    d.set_idx = it->second;
+    d.byte_off = out->byte_total;
+    d.byte_len = (uint32_t)(len[i] - h.scan_pos);
+    d.byte_span = (uint32_t)round_up(d.byte_len, kJpegHuffBytePad);
+    out->byte_total = round_up(d.byte_off + d.byte_span, kJpegHuffByteAlign);
+    d.coef_base = out->coef_total;
+    d.total_coefs = h.total_coefs;
+    out->coef_total += (int64_t)h.total_coefs;
+    d.ncomp = h.ncomp;
+    d.mcux = h.mcux;
+    d.mcuy = h.mcuy;
+    d.restart_interval = h.restart_interval;
+    for (int c = 0; c < h.ncomp; ++c) {
+      d.h[c] = h.comp[c].h;
+      d.v[c] = h.comp[c].v;
+      d.bw[c] = h.comp[c].bw;
+      d.bh[c] = h.comp[c].bh;
+      d.coef_off[c] = h.comp[c].coef_off;
+      d.td[c] = rs.td[c];
+      d.ta[c] = rs.ta[c];
+    }
+  }
+}
+
+void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, const size_t* len, uint8_t* dst) {
+  int64_t at = 0;
+  for (size_t i = 0; i < b.desc.size(); ++i) {
+    const JpegHuffDesc& d = b.desc[i];
+    if (!d.gpu) continue;
+    if (d.byte_off > at) std::memset(dst + at, 0, (size_t)(d.byte_off - at));
+    if (d.byte_len) std::memcpy(dst + d.byte_off, data[i] + (len[i] - d.byte_len), d.byte_len);
+    at = d.byte_off + d.byte_len;
+  }
+  if (b.byte_total > at) std::memset(dst + at, 0, (size_t)(b.byte_total - at));
+}
+
+const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap) {
+  int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
+  for (int i = 0; i < n; ++i) {
+    const JpegHuffDesc& d = desc[i];
+    if (!d.gpu) continue;
+    if (d.gpu != 1) return "gpu flag";
+    if (d.byte_off < byte_at || d.byte_off % kJpegHuffByteAlign != 0 || d.byte_len > d.byte_span ||
+        d.byte_span % kJpegHuffBytePad != 0 || d.byte_off + (int64_t)d.byte_span > byte_cap)
+      return "byte span outside the byte buffer";
+    byte_at = d.byte_off + (int64_t)d.byte_span;
+    if (d.set_idx < 0 || d.set_idx >= nsets) return "table set index";
+    if (d.coef_base < coef_at || d.coef_base % 64 != 0 || d.coef_base + (int64_t)d.total_coefs > coef_cap)
+      return "coefficient span outside the coefficient buffer";
+    coef_at = d.coef_base + (int64_t)d.total_coefs;
+    if ((d.ncomp != 1 && d.ncomp != 3) || d.mcux < 1 || d.mcuy < 1 || d.mcux > kJpegMaxDim / 8 + 1 ||
+        d.mcuy > kJpegMaxDim / 8 + 1 || d.restart_interval < 0 || d.restart_interval > 65535)
+      return "frame";
+    int64_t co = 0;
+    for (int c = 0; c < d.ncomp; ++c) {
+      if (d.h[c] < 1 || d.h[c] > 4 || d.v[c] < 1 || d.v[c] > 4 || d.bw[c] != d.mcux * d.h[c] ||
+          d.bh[c] != d.mcuy * d.v[c] || (int64_t)d.coef_off[c] != co || d.td[c] < 0 || d.td[c] > 3 || d.ta[c] < 0 ||
+          d.ta[c] > 3)
+        return "component layout";
+      co += (int64_t)d.bw[c] * d.bh[c] * 64;
+    }
+    if (co != (int64_t)d.total_coefs) return "coefficient count";
+  }
+  return nullptr;
+}
+
+}  // namespace idunno

@@ -1,0 +1,42 @@
+// Host packer of the device entropy stage: turns a batch of JPEG files into what
+// jpeg_huff_core.h decodes -- one contiguous byte buffer, one table buffer, one
+// descriptor per image.  Plain C++17 like jpeg_entropy.cpp (no torch, no HIP), so
+// it builds stand-alone under sanitizers (csrc/tests/jpeg_huff_core_checks.cpp).
+//
+// The marker parse is jpeg_parse_header's; the Huffman tables, which a
+// JpegHeader does not keep, are read here from the DHT segments of a file that
+// parse has already accepted.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../jpeg_huff_core.h"
+#include "jpeg_entropy.h"
+
+namespace idunno {
+
+struct JpegHuffBatch {
+  std::vector<JpegHuffDesc> desc;   // one per entry, gpu == 0 where status != JPEG_OK
+  std::vector<JpegHuffSet> sets;    // identical table sets share one entry
+  int64_t byte_total = 0;           // bytes of the batch byte buffer
+  int64_t coef_total = 0;           // int16 elements of the batch coefficient buffer
+};
+
+// Parses every entry (data[i] == nullptr: JPEG_EMPTY) and lays the batch out.
+// status[i] and hdr[i] are what jpeg_parse_header gives; an accepted image gets
+// its byte span at an aligned offset and its coefficients after its predecessors'.
+void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
+                    JpegHuffBatch* out);
+
+// Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
+// zeroes the padding between them.
+void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, const size_t* len, uint8_t* dst);
+
+// Every descriptor against the three buffers it indexes (byte_cap bytes, nsets
+// table sets, coef_cap int16 elements): nullptr when every span lies inside them
+// and the layout inside each span is consistent, else what is wrong.  Run before
+// a launch.
+const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap);
+
+}  // namespace idunno

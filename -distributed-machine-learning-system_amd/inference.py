@@ -33,7 +33,7 @@ from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
-# (device, directory) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# (device, directory, entropy_on) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
 # index only; after replacing files of a directory call drop_gpu_sources()
 _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
@@ -57,15 +57,19 @@ def drop_gpu_sources() -> None:
 
 def deeplearning(filename: str, modelname: str, start_image: int, end_image: int, *,
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
-                 data_seed: int = 1234, root: str = ".", decoder: str = "pil"):
+                 data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
     ``decoder="gpu"`` decodes the JPEG files with the native entropy decoder and
     the HIP kernels (``GpuJpegSource``: decoded images stay in HBM across calls
     by index -- ``drop_gpu_sources()`` after replacing files; without a GPU it
-    decodes with Pillow like ``"pil"``)."""
+    decodes with Pillow like ``"pil"``).  ``entropy_on="gpu"`` (with
+    ``decoder="gpu"``) also decodes the Huffman streams on the device instead of
+    on host threads; the default is ``"host"``."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
+    if entropy_on not in ("host", "gpu"):
+        raise ValueError(f"entropy_on must be 'host' or 'gpu', not {entropy_on!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -77,9 +81,10 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         src = SyntheticSource(data_seed, device)
     elif decoder == "gpu":
         with _LOCK:
-            src = _GPU_SOURCES.get((str(device), os.path.abspath(d)))
+            key = (str(device), os.path.abspath(d), entropy_on)
+            src = _GPU_SOURCES.get(key)
             if src is None:
-                src = _GPU_SOURCES[(str(device), os.path.abspath(d))] = GpuJpegSource(device, root=d)
+                src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on)
     else:
         src = JpegSource(device, root=d)
     names = class_names()
@@ -103,9 +108,11 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=0, help="images per forward (1 = reference behaviour)")
     ap.add_argument("--decoder", default="pil", choices=["pil", "gpu"],
                     help="JPEG decode: Pillow on host threads, or native entropy decode + HIP kernels")
+    ap.add_argument("--entropy", default="host", choices=["host", "gpu"],
+                    help="with --decoder gpu: Huffman decode on host threads, or on the device (one lane per image)")
     a = ap.parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
-                           decoder=a.decoder)
+                           decoder=a.decoder, entropy_on=a.entropy)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

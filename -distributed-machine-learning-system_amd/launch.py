@@ -61,7 +61,7 @@ def run_node(a) -> int:
     node = Node(cfg, name, tr, ex)
     if a.source == "jpeg":
         # real files: `put` test_<i>.JPEG into SDFS, then `inference <start> <end> <model>`
-        node.source = GpuJpegSource(sdfs=node.sdfs, device=dev)
+        node.source = GpuJpegSource(sdfs=node.sdfs, device=dev, entropy_on=a.jpeg_entropy)
     else:
         node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
                        else SyntheticSource(cfg.data_seed, dev))
@@ -85,7 +85,8 @@ def run_cluster(a) -> int:
     cfg = _cfg(a)
     shell_node = cfg.num_nodes - 1 if a.shell_node is None else a.shell_node
     procs = []
-    base = [sys.executable, "-m", "idunno.launch", "node", "--executor", a.executor, "--source", a.source]
+    base = [sys.executable, "-m", "idunno.launch", "node", "--executor", a.executor, "--source", a.source,
+            "--jpeg-entropy", a.jpeg_entropy]
     for flag, v in (("--config", a.config), ("--nodes", cfg.num_nodes), ("--base-port", cfg.base_port),
                     ("--store-root", cfg.store_root), ("--log-dir", a.log_dir)):
         if v is not None:
@@ -130,6 +131,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--standby", type=int, default=None)
     ap.add_argument("--executor", default="auto", choices=["auto", "hip", "torch", "fake"])
     ap.add_argument("--source", default="synthetic", choices=["synthetic", "sdfs", "jpeg"])
+    ap.add_argument("--jpeg-entropy", default="host", choices=["host", "gpu"],
+                    help="--source jpeg: Huffman decode on host threads, or on the device (no decode threads)")
     ap.add_argument("--shell", action="store_true")
     ap.add_argument("--shell-node", type=int, default=None)
     ap.add_argument("--no-shell", action="store_true")

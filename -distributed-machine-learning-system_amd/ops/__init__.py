@@ -15,6 +15,7 @@ __all__ = [
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
+    "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu",
 ]
 
 
@@ -347,6 +348,26 @@ def jpeg_entropy_batch(datas, threads: int = 8):
     (GIL released): (status per entry, headers, int16 coefficients on the
     host, first coefficient of each entry or -1)."""
     return load().jpeg_entropy_batch(datas, int(threads))
+
+
+def jpeg_huff_pack(datas):
+    """Parse a list of ``bytes | None`` and pack the accepted entries for the
+    device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
+    ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
+    ``bytes`` (host uint8 tensor, ``byte_total``), ``coef_total``, ``n_gpu``."""
+    return load().jpeg_huff_pack(datas)
+
+
+def jpeg_entropy_zero(coefs):
+    """Async memset of a device int16 coefficient buffer on the current stream."""
+    load().jpeg_entropy_zero(coefs)
+
+
+def jpeg_entropy_gpu(packed, dev_bytes, coefs, status):
+    """Huffman-decode a packed batch on the device, one lane per image: the
+    packed bytes in HBM -> int16 coefficients (zeroed by the caller), int32
+    status per accepted entry.  Descriptors are checked against the buffers."""
+    load().jpeg_entropy_gpu(packed, dev_bytes, coefs, status)
 
 
 def jpeg_plan(hdr, status, offs, coef_elems: int, geom, crop: int, device):

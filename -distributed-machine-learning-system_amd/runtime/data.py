@@ -626,14 +626,26 @@ class GpuJpegSource:
     ``cache_bytes`` counts images; a cached image is a row of its chunk's
     tensor (up to ``CHUNK`` images, ~38 MB), which is freed once its last row
     is evicted, so residency can exceed ``cache_bytes`` by less than one chunk
-    per partly evicted chunk."""
+    per partly evicted chunk.
+
+    ``entropy_on="gpu"`` (opt-in, default ``"host"``) decodes the Huffman
+    streams on the device too (kernels/jpeg_entropy.hip): the front thread then
+    only parses and packs, no decode threads run, and chunks are ``CHUNK_GPU``
+    images."""
 
     CHUNK = 256          # images per decode_batch call (bounds the coefficient buffers: ~0.6 MB per 500x375 image)
+    # entropy_on="gpu": one lane decodes one image, so the entropy kernel's throughput is the chunk
+    # size over one image's decode latency and it wants larger chunks than the host form.  The
+    # coefficients of a chunk live in HBM: ~0.6 MB per 500x375 image, ~1.2 GB at 2048.
+    CHUNK_GPU = 2048
 
     def __init__(self, device, root: str | None = None, sdfs=None, prefix: str = "", cache_bytes: int = 16 << 30,
-                 threads: int = 8, resize: int = 256, crop: int = HW):
+                 threads: int = 8, resize: int = 256, crop: int = HW, entropy_on: str = "host"):
         from concurrent.futures import ThreadPoolExecutor
 
+        from . import jpeg
+
+        self.entropy_on = jpeg._check_entropy_on(entropy_on)
         self.device = torch.device(device)
         self.root, self.sdfs, self.prefix = root, sdfs, prefix
         self.cache_bytes = int(cache_bytes)
@@ -695,10 +707,11 @@ class GpuJpegSource:
             # reads + Huffman decode (native threads, no GIL): runs one chunk ahead, under the
             # previous chunk's host -> HBM copy and kernels
             datas = list(self.readers.map(self._read, part))
-            return datas, (jpeg.entropy_batch(datas, self.threads) if gpu else None)
+            return datas, (jpeg.entropy_batch(datas, self.threads, self.entropy_on) if gpu else None)
 
         got, absent = {}, set()
-        parts = [idx[c:c + self.CHUNK] for c in range(0, len(idx), self.CHUNK)]
+        chunk = self.CHUNK_GPU if gpu and self.entropy_on == "gpu" else self.CHUNK
+        parts = [idx[c:c + chunk] for c in range(0, len(idx), chunk)]
         if self._front is None:
             from concurrent.futures import ThreadPoolExecutor
 
@@ -709,7 +722,7 @@ class GpuJpegSource:
             if k + 1 < len(parts):
                 nxt = self._front.submit(front, parts[k + 1])
             imgs, info = jpeg.decode_batch(datas, self.device, self.resize, self.crop, self.threads, self.stager,
-                                           entropy=ent)
+                                           entropy=ent, entropy_on=self.entropy_on)
             for name in self.seconds:
                 self.seconds[name] += info[name]
             for j, reason in info["fallbacks"]:

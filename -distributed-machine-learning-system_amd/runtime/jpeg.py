@@ -5,6 +5,14 @@ IDCT + chroma upsampling + colour conversion + resize + crop on the GPU.
     coefficients --(HbmStager: pinned ping-pong, side stream)--> HBM
     --(kernels/jpeg_decode.hip: jpeg_idct, jpeg_resize_crop)--> uint8 [B,224,224,3]
 
+With ``entropy_on="gpu"`` (opt-in) the Huffman streams are decoded on the device
+as well, one lane per image, and the file bytes cross PCIe instead of the
+coefficients (an eighth of the size):
+
+    bytes --(csrc/runtime/jpeg_huff_pack.cpp: parse + pack, no GIL)--> packed
+    bytes + tables + descriptors --(HbmStager)--> HBM --(kernels/jpeg_entropy.hip:
+    memset, jpeg_entropy_kernel)--> int16 coefficients in HBM --> the same two kernels
+
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
 crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
@@ -174,19 +182,92 @@ def _stager(device: torch.device) -> HbmStager:
     return st
 
 
-def entropy_batch(datas, threads: int = 8):
+ENTROPY_ON = ("host", "gpu")
+
+
+def _check_entropy_on(entropy_on: str) -> str:
+    if entropy_on not in ENTROPY_ON:
+        raise ValueError(f"entropy_on must be one of {ENTROPY_ON}, not {entropy_on!r}")
+    return entropy_on
+
+
+def entropy_batch(datas, threads: int = 8, entropy_on: str = "host"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
-    kernels).  Returns what ``decode_batch(..., entropy=)`` takes."""
+    kernels).  With ``entropy_on="gpu"`` it only parses the headers and packs
+    bytes, tables and descriptors for the entropy kernel (one thread, GIL
+    released as well).  Returns what ``decode_batch(..., entropy=)`` takes."""
+    _check_entropy_on(entropy_on)
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
+    if entropy_on == "gpu":
+        packed = _C().jpeg_huff_pack(datas)
+        return "gpu", datas, packed, time.perf_counter() - t0
     status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads))
     return datas, status, hdr, coefs, offs, time.perf_counter() - t0
 
 
+def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
+    """Packed bytes through the stager's side stream, memset, entropy kernel on
+    ``cur``: (device coefficients int16, device status int32 [n]); fills
+    ``h2d_s`` / ``h2d_bytes`` / ``entropy_s`` of ``info`` once the caller has
+    synchronised, through the returned closure."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    ev[0].record(stager.stream)
+    dev_bytes, done = stager._stage(packed.bytes.numpy(), (packed.byte_total,))
+    ev[1].record(stager.stream)
+    if done is not None:
+        cur.wait_event(done)
+    dev_bytes.record_stream(cur)
+    dev_coefs = torch.empty(packed.coef_total, dtype=torch.int16, device=device)
+    dev_status = torch.zeros(packed.n, dtype=torch.int32, device=device)
+    C.jpeg_entropy_zero(dev_coefs)
+    ev[2].record(cur)
+    C.jpeg_entropy_gpu(packed, dev_bytes, dev_coefs, dev_status)
+    ev[3].record(cur)
+
+    def times():
+        info["h2d_s"] = ev[0].elapsed_time(ev[1]) * 1e-3
+        info["h2d_bytes"] = int(packed.byte_total)
+        info["entropy_s"] = ev[2].elapsed_time(ev[3]) * 1e-3
+    return dev_coefs, dev_status, times
+
+
+def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8):
+    """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
+    status per entry (0: decoded), the first coefficient of each entry whose
+    header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
+    from the host decoder or, with ``entropy_on="gpu"`` on a GPU ``device``,
+    from the entropy kernel."""
+    _check_entropy_on(entropy_on)
+    C = _C()
+    datas = [None if d is None else bytes(d) for d in datas]
+    if entropy_on == "host":
+        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads))
+        return list(status), list(offs), coefs
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("entropy_on='gpu' needs a GPU device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    packed = C.jpeg_huff_pack(datas)
+    status = list(packed.status)
+    coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
+    if packed.n_gpu:
+        with torch.cuda.device(device):
+            cur = torch.cuda.current_stream(device)
+            dev_coefs, dev_status, _ = _entropy_on_device(C, packed, device, cur, _stager(device), {})
+            cur.synchronize()
+            coefs = dev_coefs.cpu()
+            for i, st in enumerate(dev_status.cpu().tolist()):
+                if status[i] == 0:
+                    status[i] = int(st)
+    return status, list(packed.offs), coefs
+
+
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
-                 stager: HbmStager | None = None, entropy=None):
+                 stager: HbmStager | None = None, entropy=None, entropy_on: str = "host"):
     """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
     ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
     resized or cropped and the result is a list of [H, W, 3] tensors (``None``
@@ -195,13 +276,28 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     host, ``entropy_s`` / ``h2d_s`` / ``idct_s`` / ``resize_s`` / ``kernel_s``
     the seconds of the native Huffman decode (wall), the coefficient copy and
     the kernels (device events).  ``entropy``: the result of ``entropy_batch``
-    on the same ``datas``, when the caller ran that ahead."""
+    on the same ``datas``, when the caller ran that ahead.
+
+    ``entropy_on="gpu"`` moves the Huffman decode to the device (default
+    ``"host"``; ignored on a CPU device, and when ``entropy`` was prepared the
+    form it was prepared in decides): the host only parses headers and packs,
+    ``h2d_s`` is then the copy of the file bytes (``info["h2d_bytes"]``),
+    ``entropy_s`` the entropy kernel's device-event time and ``pack_s`` the
+    host's parse + pack (wall).  An image the kernel flags is a ``"corrupt"``
+    fallback exactly like one the host decoder refuses.  ``info["entropy_on"]``
+    names the form in effect (on a CPU device: the one asked for; nothing
+    native runs there)."""
+    _check_entropy_on(entropy_on)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
-    datas = [None if d is None else bytes(d) for d in datas] if entropy is None else entropy[0]
+    on_gpu = entropy_on == "gpu" if entropy is None else isinstance(entropy[0], str)
+    if entropy is None:
+        datas = [None if d is None else bytes(d) for d in datas]
+    else:
+        datas = entropy[1] if on_gpu else entropy[0]
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
-            "gpu_images": 0}
+            "gpu_images": 0, "entropy_on": "gpu" if on_gpu else "host"}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -218,7 +314,13 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     C = _C()
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    _, status, hdr, coefs, offs, info["entropy_s"] = entropy if entropy is not None else entropy_batch(datas, threads)
+    packed = None
+    if on_gpu:
+        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, "gpu")
+        status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
+    else:
+        _, status, hdr, coefs, offs, info["entropy_s"] = entropy if entropy is not None else entropy_batch(datas, threads)
+        coef_elems = coefs.numel()
     geom = None
     if not full:
         hv = hdr.numpy().view(np.int32)           # JpegHeader starts with int W, H
@@ -234,16 +336,19 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         geom = torch.tensor(rows, dtype=torch.int64).view(n, 4)
     with torch.cuda.device(device):
         cur = torch.cuda.current_stream(device)
-        plan = C.jpeg_plan(hdr, status, offs, coefs.numel(), geom, 0 if full else int(crop), device)
+        plan = C.jpeg_plan(hdr, status, offs, coef_elems, geom, 0 if full else int(crop), device)
         out = torch.zeros(max(plan.out_bytes, 0) if full else n * crop * crop * 3, dtype=torch.uint8, device=device)
         if plan.n_gpu:
             stager = stager or _stager(device)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-            ev[0].record(stager.stream)
-            dev_coefs, done = stager._stage(coefs.numpy(), (coefs.numel() * 2,))
-            ev[1].record(stager.stream)
-            cur.wait_event(done)
-            dev_coefs.record_stream(cur)
+            if on_gpu:
+                dev_coefs, dev_status, entropy_times = _entropy_on_device(C, packed, device, cur, stager, info)
+            else:
+                ev[0].record(stager.stream)
+                dev_coefs, done = stager._stage(coefs.numpy(), (coefs.numel() * 2,))
+                ev[1].record(stager.stream)
+                cur.wait_event(done)
+                dev_coefs.record_stream(cur)
             planes = torch.empty(plan.plane_bytes, dtype=torch.uint8, device=device)
             ev[2].record(cur)
             C.jpeg_idct(plan, dev_coefs.view(torch.int16), planes)
@@ -251,11 +356,21 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
             C.jpeg_resize_crop(plan, planes, out)
             ev[4].record(cur)
             ev[4].synchronize()
-            info["h2d_s"] = ev[0].elapsed_time(ev[1]) * 1e-3
+            info["gpu_images"] = int(plan.n_gpu)
+            if on_gpu:
+                entropy_times()
+                # the kernel's verdicts: a flagged image was planned and run through the two kernels on
+                # whatever it decoded before the flag (bounded, like any coefficients); the fallback loop
+                # below overwrites its output
+                for i, st in enumerate(dev_status.cpu().tolist()):
+                    if status[i] == 0 and st != 0:
+                        status[i] = int(st)
+                        info["gpu_images"] -= 1
+            else:
+                info["h2d_s"] = ev[0].elapsed_time(ev[1]) * 1e-3
             info["idct_s"] = ev[2].elapsed_time(ev[3]) * 1e-3
             info["resize_s"] = ev[3].elapsed_time(ev[4]) * 1e-3
             info["kernel_s"] = info["idct_s"] + info["resize_s"]
-            info["gpu_images"] = int(plan.n_gpu)
         imgs = []
         if not full:
             out = out.view(n, crop, crop, 3)

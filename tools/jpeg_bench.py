@@ -10,7 +10,13 @@ alternating three times, reports images/s of
   * ``GpuJpegSource.get``  warm (everything resident),
 
 and the cold path's split into entropy decode (host wall time), H2D and the two
-kernels (device events).  Needs a GPU: without one it exits with an error.
+kernels (device events).  Then the entropy stage on the host against the
+opt-in stage on the device (``entropy_on="gpu"``), cold passes alternating in
+the same process: host threads ``--threads`` and 2 (one rank's share when 8
+ranks split 16 CPUs), device form at each ``--gpu-chunks`` size; per pass
+images/s, entropy time, H2D bytes and time, and host CPU seconds
+(``time.process_time``: all threads of the process).  Needs a GPU: without one
+it exits with an error.
 
     python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
 """
@@ -52,6 +58,8 @@ def main(argv=None) -> int:
     ap.add_argument("--images", type=int, default=2000)
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--gpu-chunks", default="256,1024,2048", help="GpuJpegSource.CHUNK_GPU values of the device entropy rows")
+    ap.add_argument("--entropy-only", action="store_true", help="only the host / device entropy comparison")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
 
@@ -90,45 +98,85 @@ def main(argv=None) -> int:
         w = min(n, 64)
         timed(lambda: pil.get(0, w - 1))
         timed(lambda: GpuJpegSource(dev, root=d, threads=a.threads).get(0, w - 1))
-        rates = {"pil": [], "cold": [], "warm": []}
-        split = {"entropy_s": [], "h2d_s": [], "idct_s": [], "resize_s": []}
-        ref = None
+        if not a.entropy_only:
+            rates = {"pil": [], "cold": [], "warm": []}
+            split = {"entropy_s": [], "h2d_s": [], "idct_s": [], "resize_s": []}
+            ref = None
+            for r in range(a.reps):
+                dt, x = timed(lambda: pil.get(0, n - 1))
+                rates["pil"].append(n / dt)
+                gpu = GpuJpegSource(dev, root=d, threads=a.threads)
+                dt, y = timed(lambda: gpu.get(0, n - 1))
+                rates["cold"].append(n / dt)
+                for k in split:
+                    split[k].append(gpu.seconds[k])
+                assert gpu.decoded == n and gpu.fallbacks == 0
+                dt, z = timed(lambda: gpu.get(0, n - 1))
+                rates["warm"].append(n / dt)
+                assert gpu.decoded == n and torch.equal(y, z)
+                if ref is None:
+                    diff = (x.int() - y.int()).abs()
+                    ref = (int(diff.max()), float(diff.float().mean()))
+                say(f"rep {r}: JpegSource {rates['pil'][-1]:9.1f} img/s | GpuJpegSource cold {rates['cold'][-1]:9.1f} img/s | "
+                    f"warm {rates['warm'][-1]:12.1f} img/s")
+                del x, y, z, gpu
+            say(f"GPU output vs Pillow output over {n} images: max |diff| {ref[0]}, mean {ref[1]:.4f}")
+            for k, name in (("pil", "JpegSource.get (Pillow, threads)"), ("cold", "GpuJpegSource.get cold"),
+                            ("warm", "GpuJpegSource.get warm")):
+                v = rates[k]
+                say(f"{name:34s} median {np.median(v):12.1f} img/s  min {min(v):12.1f}  max {max(v):12.1f}  "
+                    f"spread {100 * (max(v) - min(v)) / np.median(v):.1f} %")
+            say(f"cold / Pillow = {np.median(rates['cold']) / np.median(rates['pil']):.2f}x (medians)")
+            for k, name in (("entropy_s", "entropy decode (host, wall)"), ("h2d_s", "H2D of coefficients (events)"),
+                            ("idct_s", "jpeg_idct_kernel (events)"), ("resize_s", "jpeg_resize_crop_kernel (events)")):
+                v = split[k]
+                say(f"  cold split: {name:34s} median {1e3 * np.median(v):9.2f} ms  ({1e6 * np.median(v) / n:8.2f} us/image)")
+            # bytes the kernels move per image: 500x375 4:2:0 = 32x24 MCUs of 6 blocks
+            blocks = 32 * 24 * 6
+            idct_b = blocks * (128 + 64)
+            say(f"  jpeg_idct_kernel: {blocks} blocks/image, {idct_b} B/image read+written -> "
+                f"{n * idct_b / np.median(split['idct_s']) / 1e9:.1f} GB/s")
+            say(f"  jpeg_resize_crop_kernel: {224 * 224 * 3} B/image written -> "
+                f"{n * 224 * 224 * 3 / np.median(split['resize_s']) / 1e9:.2f} GB/s of output")
+        # ---- entropy stage: host threads against the device kernel, same process, alternating ----
+        forms = [(f"host, {a.threads} threads", "host", a.threads, None), ("host, 2 threads", "host", 2, None)]
+        forms += [(f"gpu, chunk {c}", "gpu", a.threads, int(c)) for c in a.gpu_chunks.split(",") if c]
+
+        def source(on, threads, chunk):
+            src = GpuJpegSource(dev, root=d, threads=threads, entropy_on=on)
+            if chunk is not None:
+                src.CHUNK_GPU = chunk
+            return src
+
+        want = source("host", a.threads, None).get(0, n - 1)
+        for _, on, threads, chunk in forms:                     # warm-up of every form; the outputs must agree
+            got = source(on, threads, chunk).get(0, n - 1)
+            assert torch.equal(got, want), (on, threads, chunk)
+            del got
+        del want
+        res = {name: {"rate": [], "entropy_s": [], "h2d_s": [], "h2d_b": [], "cpu_s": []} for name, *_ in forms}
         for r in range(a.reps):
-            dt, x = timed(lambda: pil.get(0, n - 1))
-            rates["pil"].append(n / dt)
-            gpu = GpuJpegSource(dev, root=d, threads=a.threads)
-            dt, y = timed(lambda: gpu.get(0, n - 1))
-            rates["cold"].append(n / dt)
-            for k in split:
-                split[k].append(gpu.seconds[k])
-            assert gpu.decoded == n and gpu.fallbacks == 0
-            dt, z = timed(lambda: gpu.get(0, n - 1))
-            rates["warm"].append(n / dt)
-            assert gpu.decoded == n and torch.equal(y, z)
-            if ref is None:
-                diff = (x.int() - y.int()).abs()
-                ref = (int(diff.max()), float(diff.float().mean()))
-            say(f"rep {r}: JpegSource {rates['pil'][-1]:9.1f} img/s | GpuJpegSource cold {rates['cold'][-1]:9.1f} img/s | "
-                f"warm {rates['warm'][-1]:12.1f} img/s")
-            del x, y, z, gpu
-        say(f"GPU output vs Pillow output over {n} images: max |diff| {ref[0]}, mean {ref[1]:.4f}")
-        for k, name in (("pil", "JpegSource.get (Pillow, threads)"), ("cold", "GpuJpegSource.get cold"),
-                        ("warm", "GpuJpegSource.get warm")):
-            v = rates[k]
-            say(f"{name:34s} median {np.median(v):12.1f} img/s  min {min(v):12.1f}  max {max(v):12.1f}  "
-                f"spread {100 * (max(v) - min(v)) / np.median(v):.1f} %")
-        say(f"cold / Pillow = {np.median(rates['cold']) / np.median(rates['pil']):.2f}x (medians)")
-        for k, name in (("entropy_s", "entropy decode (host, wall)"), ("h2d_s", "H2D of coefficients (events)"),
-                        ("idct_s", "jpeg_idct_kernel (events)"), ("resize_s", "jpeg_resize_crop_kernel (events)")):
-            v = split[k]
-            say(f"  cold split: {name:34s} median {1e3 * np.median(v):9.2f} ms  ({1e6 * np.median(v) / n:8.2f} us/image)")
-        # bytes the kernels move per image: 500x375 4:2:0 = 32x24 MCUs of 6 blocks
-        blocks = 32 * 24 * 6
-        idct_b = blocks * (128 + 64)
-        say(f"  jpeg_idct_kernel: {blocks} blocks/image, {idct_b} B/image read+written -> "
-            f"{n * idct_b / np.median(split['idct_s']) / 1e9:.1f} GB/s")
-        say(f"  jpeg_resize_crop_kernel: {224 * 224 * 3} B/image written -> "
-            f"{n * 224 * 224 * 3 / np.median(split['resize_s']) / 1e9:.2f} GB/s of output")
+            for name, on, threads, chunk in forms:
+                src = source(on, threads, chunk)
+                c0 = time.process_time()
+                dt, y = timed(lambda: src.get(0, n - 1))
+                cpu = time.process_time() - c0
+                assert src.decoded == n and src.fallbacks == 0
+                v = res[name]
+                v["rate"].append(n / dt)
+                v["entropy_s"].append(src.seconds["entropy_s"])
+                v["h2d_s"].append(src.seconds["h2d_s"])
+                v["h2d_b"].append(src.stager.bytes_staged)
+                v["cpu_s"].append(cpu)
+                say(f"entropy rep {r}: {name:18s} {n / dt:9.1f} img/s  entropy {1e3 * src.seconds['entropy_s']:8.2f} ms  "
+                    f"H2D {src.stager.bytes_staged / 1e6:8.1f} MB in {1e3 * src.seconds['h2d_s']:7.2f} ms  host CPU {cpu:6.3f} s")
+                del y, src
+        say("entropy stage, cold GpuJpegSource.get (entropy: host wall over the decode threads / device events of the kernel):")
+        for name, *_ in forms:
+            v = res[name]
+            say(f"  {name:18s} median {np.median(v['rate']):9.1f} img/s  min {min(v['rate']):9.1f}  max {max(v['rate']):9.1f} | "
+                f"entropy {1e3 * np.median(v['entropy_s']):8.2f} ms | H2D {np.median(v['h2d_b']) / 1e6:8.1f} MB "
+                f"{1e3 * np.median(v['h2d_s']):7.2f} ms | host CPU {np.median(v['cpu_s']):6.3f} s")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
