@@ -209,17 +209,15 @@ int conv_glds_pick(int M, int Cout);
 // psum = [8][8][64] 2D prefix sums of w * c_c over (kh, kw); y = split [B][Hp][Wp][128]
 // fused split AlexNet stem: uint8 -> conv 11x11/4 (exact-u8, split weights) -> ReLU -> max pool 3x3/2
 // -> split [B][Hp][Wp][128]; w = [2][64][17*32] (models/packed.py pack_alex_stem_split)
+// form: 0 one-half workgroups (one per CU split, two per CU fp16), 1 phased, -1 the default
+// (split: phased, fp16: one-half); any other value returns false
 bool alex_stem_u8_f16_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum,
                              float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
-                             long long start_off, long long max_start, long long sub, hipStream_t st);
-void set_astem_f16_two_wg(bool on);
-void set_astem_ahead(bool on);   // A/B switch: patch loads one tile ahead (1) or after the MFMA loop
-void set_astem_phased(bool on);  // A/B switch: the phased two-half kernel (default) or the one-half form
-void set_astem_variant(int v);   // tools/astem_ablate.py: 0 production, 16 loads after the loop, 1/2/4/6 ablations
+                             long long start_off, long long max_start, long long sub, int form, hipStream_t st);
 bool alex_stem_split_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum,
                             float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
-                            long long start_off, long long max_start, long long sub, int* ovf, hipStream_t st);
-void set_stem_prewait(bool on);  // A/B switch: vmcnt(0) ahead of the split stem's tile loop
+                            long long start_off, long long max_start, long long sub, int* ovf, int form,
+                            hipStream_t st);
 void stem_split_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum, float acc_scale,
                        half_t* y, int B, int H, int W, const long long* start_idx, long long start_off,
                        long long max_start, long long sub, int* ovf, hipStream_t st);
@@ -249,7 +247,7 @@ void softmax_top1_launch(const float* logits, int ld, int N, int rows, int* cls,
                          const int* ovf, hipStream_t st);
 
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
-// One descriptor per image on the device; the host (bindings.cpp jpeg_plan) has
+// One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.
 struct alignas(16) JpegImageDesc {
   unsigned short q[3][64];   // quantisation tables, natural order

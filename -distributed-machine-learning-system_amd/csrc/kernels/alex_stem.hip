@@ -32,7 +32,7 @@
 // pixels) is staged in LDS as [row][pixel][4] fp16; the border prefix sums live in
 // LDS too.
 //
-// Two forms (set_astem_variant; B = 500, tools/astem_ablate.py):
+// Two forms (the launchers' `form` argument; figures at B = 500):
 //   alex_stem_split_kernel   one 256-thread workgroup per CU, A hi + lo in 136 VGPRs,
 //                            accumulators in AGPRs, patch loads one tile ahead:
 //                            MFMA loop, staging and epilogue run back to back
@@ -274,13 +274,11 @@ __device__ __forceinline__ void astem_epilogue(float4v (&acc)[astem::CRY], const
   if (bad && g.ovf != nullptr) *g.ovf = 1;
 }
 
-// ABL: ablation bits for tools/astem_ablate.py (0 in production): 1 no MFMA loop,
-// 2 no epilogue (accumulators kept alive by a never-taken store), 4 no patch staging
 // F16: the fp16 programs' stem (hi MFMA only, fp16 out) at two workgroups per CU:
 // without the A lo fragments a wave fits 256 registers, and with its MFMA loop half
 // as long the epilogue/staging work dominates, which two independent workgroups
 // overlap without phase barriers
-template <bool AHEAD, int ABL = 0, bool F16 = false>
+template <bool F16 = false>
 __global__ void __launch_bounds__(256, F16 ? 2 : 1)
 alex_stem_split_kernel(const uint8_t* __restrict__ img, const half_t* __restrict__ w, const float* __restrict__ bias,
                        const float* __restrict__ psum, float acc_scale, half_t* __restrict__ y, const AStemGeom g,
@@ -322,7 +320,7 @@ alex_stem_split_kernel(const uint8_t* __restrict__ img, const half_t* __restrict
     reinterpret_cast<float4v*>(ps)[i] = reinterpret_cast<const float4v*>(psum)[i];
   astem_store(smem, tid, q);
   int tn = t + gridDim.x;
-  if (AHEAD && tn < g.ntiles) astem_load(img, g, tn, tid, q);   // one tile ahead (held in AGPRs)
+  if (tn < g.ntiles) astem_load(img, g, tn, tid, q);   // one tile ahead (held in AGPRs)
   __syncthreads();
 
   // per-lane patch byte offsets (conv row 0): main steps read pixels
@@ -350,7 +348,6 @@ alex_stem_split_kernel(const uint8_t* __restrict__ img, const half_t* __restrict
     astem_read_b(smem, 0, mainb, tailb, trow, bf[0]);
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
-      if (ABL & 1) break;
       if (s + 1 < NKS) astem_read_b(smem, s + 1, mainb, tailb, trow, bf[(s + 1) & 1]);
 #pragma unroll
       for (int r = 0; r < CRY; ++r)
@@ -364,35 +361,15 @@ alex_stem_split_kernel(const uint8_t* __restrict__ img, const half_t* __restrict
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();                           // every wave's patch reads of tile t are done
-    // the next tile's patch loads go out now (not a tile ahead: the 136 A registers, 36
-    // accumulators and 9 B fragments leave no room to hold them across the MFMA loop)
-    // and land while this tile's epilogue runs
+    // the next tile's patch (loaded one tile ahead) goes to LDS now
     const int tnext = tn;
-    if constexpr (AHEAD) {
-      if (!(ABL & 4) && tnext < g.ntiles) astem_store(smem, tid, q);
-      tn = tnext + gridDim.x;
-    } else {
-      tn = tnext + gridDim.x;
-      if (tnext < g.ntiles) astem_load(img, g, tnext, tid, q);
-    }
-
-    if constexpr ((ABL & 2) != 0) {
-      if (g.B < 0) {                           // never: keeps the MFMA loop alive
-#pragma unroll
-        for (int r = 0; r < CRY; ++r) *reinterpret_cast<float4v*>(y + 8 * r) = acc[r];
-      }
-      if (AHEAD && !(ABL & 4) && tn < g.ntiles) astem_load(img, g, tn, tid, q);
-      __syncthreads();
-      if (tnext >= g.ntiles) break;
-      t = tnext;
-      continue;
-    }
+    if (tnext < g.ntiles) astem_store(smem, tid, q);
+    tn = tnext + gridDim.x;
     astem_epilogue<F16>(acc, g, b, py0, px0, cx, c0, ps, inv_scale, acc_scale, bv, y);
-    if (!AHEAD && tnext < g.ntiles) astem_store(smem, tid, q);
     // the loads of the tile after next go out behind this tile's border-correction
     // loads and output stores (vmcnt retires in order: those waits do not cover them)
     // and land during tile tnext's MFMA loop
-    if (AHEAD && !(ABL & 4) && tn < g.ntiles) astem_load(img, g, tn, tid, q);
+    if (tn < g.ntiles) astem_load(img, g, tn, tid, q);
     __syncthreads();                           // tile tnext's patch is in LDS
     if (tnext >= g.ntiles) break;
     t = tnext;
@@ -405,7 +382,7 @@ alex_stem_split_kernel(const uint8_t* __restrict__ img, const half_t* __restrict
 // its next patch, then the roles swap (one workgroup barrier per phase).  SIMD k holds
 // wave k of each half, so one wave's VALU/LDS/global work issues between the other's
 // MFMAs instead of after them (the one-half form runs them back to back: MFMA loop
-// 157 us + staging ~60 + epilogue ~90 at B = 500, tools/astem_ablate.py).  Two waves
+// 157 us + staging ~60 + epilogue ~90 at B = 500).  Two waves
 // per SIMD leave 256 registers a wave: the A lo fragments move to LDS (one 16-byte read
 // per K step, reused by 9 MFMAs) next to the two patches and the prefix sums.
 namespace astem {
@@ -415,10 +392,10 @@ constexpr int LDS2_BYTES = AL_OFF + 64 * NKS * 32 * 2;   // 158,784 B
 static_assert(LDS2_BYTES <= 160 * 1024, "one workgroup per CU");
 }  // namespace astem
 
-// ABL: ablations (tools/astem_ablate.py): 1 no MFMA loop, 2 no E phase.  F16: the fp16
+// F16: the fp16
 // programs' stem in the same exact-u8 form -- hi MFMA only (w' rounded to fp16 once,
 // u exact), fp16 output
-template <int ABL = 0, bool F16 = false>
+template <bool F16 = false>
 __global__ void __launch_bounds__(512, 1)
 alex_stem_split_kernel2(const uint8_t* __restrict__ img, const half_t* __restrict__ w, const float* __restrict__ bias,
                         const float* __restrict__ psum, float acc_scale, half_t* __restrict__ y, const AStemGeom g,
@@ -477,10 +454,6 @@ alex_stem_split_kernel2(const uint8_t* __restrict__ img, const half_t* __restric
       // ---- C(k): the MFMA loop of tile t0 + k * stride on this half's patch ----
 #pragma unroll
       for (int r = 0; r < CRY; ++r) acc[r] = float4v{0.f, 0.f, 0.f, 0.f};
-      if constexpr ((ABL & 1) != 0) {
-#pragma unroll
-        for (int r = 0; r < CRY; ++r) acc[r] = *reinterpret_cast<const float4v*>(patch + 64 * r + 16 * fch);
-      } else {
       half8v bf[2][CRY];
       half8v al_s[2];
       astem_read_b(patch, 0, mainb, tailb, trow, bf[0]);
@@ -501,18 +474,9 @@ alex_stem_split_kernel2(const uint8_t* __restrict__ img, const half_t* __restric
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      }
     } else if (d >= 1 && (d & 1) && ((d - 1) >> 1) < nh) {
       // ---- E(k): stage tile k+1's patch, send tile k+2's loads, epilogue of tile k ----
       const int kk = (d - 1) >> 1;
-      if constexpr ((ABL & 2) != 0) {
-        if (g.B < 0) {                           // never: keeps the MFMA loop alive
-#pragma unroll
-          for (int r = 0; r < CRY; ++r) *reinterpret_cast<float4v*>(y + 8 * r) = acc[r];
-        }
-        __syncthreads();
-        continue;
-      }
       if (kk + 1 < nh) astem_store(patch, htid, q);
       if (kk + 2 < nh) astem_load(img, g, t0 + (kk + 2) * stride, htid, q);
       int b, py0, px0;
@@ -541,70 +505,50 @@ static bool astem_geom(AStemGeom& g, int B, int H, int W, const uint8_t* img, in
   return true;
 }
 
-// fp16 form: two one-half workgroups per CU (default, AlexNet fp16 b500 +1.8 % over the
-// phased halves: profiles/r6w_ab_alex_stem_f16_two_wg_b500.log) or the phased kernel
-static int g_astem_f16_two_wg = 1;
-void set_astem_f16_two_wg(bool on) { g_astem_f16_two_wg = on; }
-
-// fp16 programs: the phased exact-u8 stem, hi MFMA only, fp16 [B][Hp][Wp][64] out
-bool alex_stem_u8_f16_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum,
-                             float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
-                             long long start_off, long long max_start, long long sub, hipStream_t st) {
+// `form` picks the kernel per call (no process-global switch): 0 one-half workgroups
+// (alex_stem_split_kernel: one per CU for split, two per CU for fp16), 1 phased
+// (alex_stem_split_kernel2), -1 the default of the launcher.  Other values: false.
+template <bool F16>
+static bool astem_launch(int form, const uint8_t* img, const half_t* w, const float* bias, const float* psum,
+                         float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
+                         long long start_off, long long max_start, long long sub, int* ovf, hipStream_t st) {
   using namespace astem;
   AStemGeom g;
-  if (!astem_geom(g, B, H, W, img, nullptr)) return false;
+  if ((form != 0 && form != 1) || !astem_geom(g, B, H, W, img, ovf)) return false;
   if (g.ntiles <= 0) return true;
   const int per = device_cu_count();
-  if (g_astem_f16_two_wg) {
-    const int grid = g.ntiles < 2 * per ? g.ntiles : 2 * per;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(alex_stem_split_kernel<true, 0, true>), dim3(grid), dim3(256), LDS_BYTES, st,
-                       img, w, bias, psum, acc_scale, y, g, start_idx, start_off, max_start, sub);
+  if (form == 1) {
+    const int grid2 = (g.ntiles + 1) / 2 < per ? (g.ntiles + 1) / 2 : per;
+    auto k2 = alex_stem_split_kernel2<F16>;
+    ensure_lds_attr(reinterpret_cast<const void*>(k2), LDS2_BYTES);
+    hipLaunchKernelGGL(k2, dim3(grid2), dim3(512), LDS2_BYTES, st, img, w, bias, psum, acc_scale, y, g, start_idx,
+                       start_off, max_start, sub);
     return true;
   }
-  const int grid2 = (g.ntiles + 1) / 2 < per ? (g.ntiles + 1) / 2 : per;
-  auto k2 = alex_stem_split_kernel2<0, true>;
-  ensure_lds_attr(reinterpret_cast<const void*>(k2), LDS2_BYTES);
-  hipLaunchKernelGGL(k2, dim3(grid2), dim3(512), LDS2_BYTES, st, img, w, bias, psum, acc_scale, y, g, start_idx,
-                     start_off, max_start, sub);
+  const int cap = F16 ? 2 * per : per;        // split: one workgroup per CU (all 512 registers)
+  const int grid = g.ntiles < cap ? g.ntiles : cap;
+  hipLaunchKernelGGL(alex_stem_split_kernel<F16>, dim3(grid), dim3(256), LDS_BYTES, st, img, w, bias, psum, acc_scale,
+                     y, g, start_idx, start_off, max_start, sub);
   return true;
 }
 
-static int g_astem_variant = 64;
-void set_astem_ahead(bool on) { g_astem_variant = on ? 0 : 16; }
-void set_astem_phased(bool on) { g_astem_variant = on ? 64 : 0; }
-void set_astem_variant(int v) { g_astem_variant = v; }
+// fp16 programs: the exact-u8 stem, hi MFMA only, fp16 [B][Hp][Wp][64] out.  Default: two
+// one-half workgroups per CU (AlexNet fp16 b500 +1.8 % over the phased halves:
+// profiles/r6w_ab_alex_stem_f16_two_wg_b500.log)
+bool alex_stem_u8_f16_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum,
+                             float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
+                             long long start_off, long long max_start, long long sub, int form, hipStream_t st) {
+  return astem_launch<true>(form < 0 ? 0 : form, img, w, bias, psum, acc_scale, y, B, H, W, start_idx, start_off,
+                            max_start, sub, nullptr, st);
+}
 
+// split programs.  Default: phased (profiles/r6x3_ab_alex_stem_phased_*)
 bool alex_stem_split_launch(const uint8_t* img, const half_t* w, const float* bias, const float* psum,
                             float acc_scale, half_t* y, int B, int H, int W, const long long* start_idx,
-                            long long start_off, long long max_start, long long sub, int* ovf, hipStream_t st) {
-  using namespace astem;
-  AStemGeom g;
-  if (!astem_geom(g, B, H, W, img, ovf)) return false;
-  if (g.ntiles <= 0) return true;
-  const int per = device_cu_count();          // one workgroup per CU (all 512 registers)
-  const int grid = g.ntiles < per ? g.ntiles : per;
-  auto k = alex_stem_split_kernel<true>;
-  switch (g_astem_variant) {
-    case 16: k = alex_stem_split_kernel<false>; break;
-    case 1: k = alex_stem_split_kernel<true, 1>; break;
-    case 2: k = alex_stem_split_kernel<true, 2>; break;
-    case 4: k = alex_stem_split_kernel<true, 4>; break;
-    case 6: k = alex_stem_split_kernel<true, 6>; break;
-    default: break;
-  }
-  if (g_astem_variant >= 64) {
-    const int grid2 = (g.ntiles + 1) / 2 < per ? (g.ntiles + 1) / 2 : per;
-    auto k2 = alex_stem_split_kernel2<0>;
-    if (g_astem_variant == 65) k2 = alex_stem_split_kernel2<1>;
-    if (g_astem_variant == 66) k2 = alex_stem_split_kernel2<2>;
-    ensure_lds_attr(reinterpret_cast<const void*>(k2), LDS2_BYTES);
-    hipLaunchKernelGGL(k2, dim3(grid2), dim3(512), LDS2_BYTES, st, img, w, bias, psum, acc_scale,
-                       y, g, start_idx, start_off, max_start, sub);
-    return true;
-  }
-  hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS_BYTES, st, img, w, bias, psum, acc_scale, y, g, start_idx,
-                     start_off, max_start, sub);
-  return true;
+                            long long start_off, long long max_start, long long sub, int* ovf, int form,
+                            hipStream_t st) {
+  return astem_launch<false>(form < 0 ? 1 : form, img, w, bias, psum, acc_scale, y, B, H, W, start_idx, start_off,
+                             max_start, sub, ovf, st);
 }
 
 }  // namespace idunno

@@ -592,6 +592,9 @@ class HipRunner:
         self.pack3 = pack3           # fp32 RGB stems on packed rows (conv_f32.hip mode 2)
         self.pack3_f16 = False       # fp16 AlexNet conv1 on packed rows (measured net-neutral, see _logits)
         self.side_down = False       # downsample conv on a second stream (A/B: tools/ab_flag.py --attr)
+        # fused AlexNet stem kernel form (ops.alex_stem_split / alex_stem_u8_f16): -1 the default, 0 one-half
+        # workgroups, 1 phased (A/B: tools/ab_flag.py --attr astem_form --values 0,1 --model alexnet)
+        self.astem_form = -1
         self.stem_parts: int | None = None   # fp32 ResNet: stem + maxpool on batch parts (None = 1)
         # fp32 ResNets: residual stages on split-fp16 convs (conv_glds SPLIT:
         # hi*hi + hi*lo + lo*hi on the f16 MFMA, fp32-accurate) instead of the
@@ -742,7 +745,7 @@ class HipRunner:
         p3 = (first is not None and native and self.pack3_f16 and first.p3 is not None and not astem)
         if astem:
             x = o.alex_stem_u8_f16(img_u8, first.fs, first.fs_bias, first.fs_psum, first.fs_scale, start, batch,
-                                   start_offset)
+                                   start_offset, form=self.astem_form)
         elif p3:
             # AlexNet conv1 (11x11/4) on packed fp16 rows through conv_glds (K 448
             # vs 704 for NHWC4 on the register-staged conv_igemm): conv 290 -> 220
@@ -1032,7 +1035,7 @@ class HipRunner:
         if self.fuse_stem and first.fs is not None and first.kh == 11 and first.relu and feats \
                 and feats[0][0] == "pool" and tuple(feats[0][1]) == (3, 2, 0):
             x = o.alex_stem_split(img_u8, first.fs, first.fs_bias, first.fs_psum, first.fs_scale, start, batch,
-                                  start_offset)
+                                  start_offset, form=self.astem_form)
             feats = feats[1:]
         else:
             x = self._stem_f32(first, img_u8, start, batch, start_offset)

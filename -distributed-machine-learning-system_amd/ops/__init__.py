@@ -91,18 +91,22 @@ def stem_split(img_u8, w, bias, psum, acc_scale: float, start=None, batch: int =
 
 
 def alex_stem_split(img_u8, w, bias, psum, acc_scale: float, start=None, batch: int = -1, start_offset: int = 0,
-                    window: int = -1, sub: int = 0):
+                    window: int = -1, sub: int = 0, form: int = -1):
     """fp32-accurate fused AlexNet stem on split fp16: uint8 [B,224,224,3] ->
     split [B,27,27,128] (normalise, conv 11x11/4 pad 2 + bias, ReLU, max pool
-    3x3/2); ``w, acc_scale, bias, psum`` = models.packed.pack_alex_stem_split(w, b)."""
-    return load().alex_stem_split(img_u8, w, bias, psum, acc_scale, start, batch, start_offset, window, sub)
+    3x3/2); ``w, acc_scale, bias, psum`` = models.packed.pack_alex_stem_split(w, b).
+    ``form``: the kernel form, -1 the default (phased), 0 one-half workgroups
+    (one per CU), 1 phased."""
+    return load().alex_stem_split(img_u8, w, bias, psum, acc_scale, start, batch, start_offset, window, sub, form)
 
 
 def alex_stem_u8_f16(img_u8, w, bias, psum, acc_scale: float, start=None, batch: int = -1, start_offset: int = 0,
-                     window: int = -1, sub: int = 0):
+                     window: int = -1, sub: int = 0, form: int = -1):
     """fp16 fused AlexNet stem in the exact-u8 form (hi MFMA only): uint8
-    [B,224,224,3] -> fp16 [B,27,27,64]; operands as ``alex_stem_split``."""
-    return load().alex_stem_u8_f16(img_u8, w, bias, psum, acc_scale, start, batch, start_offset, window, sub)
+    [B,224,224,3] -> fp16 [B,27,27,64]; operands as ``alex_stem_split``.
+    ``form``: -1 the default (one-half workgroups), 0 one-half workgroups (two
+    per CU), 1 phased."""
+    return load().alex_stem_u8_f16(img_u8, w, bias, psum, acc_scale, start, batch, start_offset, window, sub, form)
 
 
 def stem_u8_f16(img_u8, w, bias, psum, acc_scale: float, start=None, batch: int = -1, start_offset: int = 0,

@@ -548,12 +548,14 @@ def test_stem_u8_f16_vs_fp32(ops, B, H):
     _check(y, ref)
 
 
-@pytest.mark.parametrize("two_wg", [False, True])
+@pytest.mark.parametrize("form", [1, 0])
 @pytest.mark.parametrize("B,H,W", [(3, 224, 224), (2, 100, 131), (1, 31, 23)])
-def test_alex_stem_u8_f16_vs_fp32(ops, B, H, W, two_wg):
-    """fp16 fused AlexNet stem (hi MFMA only; both kernel forms) vs the fp32 conv 11x11/4
-    + ReLU + max pool 3x3/2 of the same image; device-side window included."""
+def test_alex_stem_u8_f16_vs_fp32(ops, B, H, W, form):
+    """fp16 fused AlexNet stem (hi MFMA only; both kernel forms: 1 phased halves, 0 two one-half
+    workgroups per CU = the default) vs the fp32 conv 11x11/4 + ReLU + max pool 3x3/2 of the same
+    image; device-side window included."""
     from idunno.models.packed import pack_alex_stem_split
+    from idunno.models.reference import preprocess_u8
 
     torch.manual_seed(H + B + 2)
     img = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device=DEV)
@@ -561,24 +563,26 @@ def test_alex_stem_u8_f16_vs_fp32(ops, B, H, W, two_wg):
     b = torch.randn(64) * 0.1
     fs, scale, bias, psum = pack_alex_stem_split(w.double(), b.double())
     fs, bias, psum = fs.to(DEV), bias.to(DEV), psum.to(DEV)
-    ops.load().set_astem_f16_two_wg(two_wg)      # the kernel form (phased halves / two one-half workgroups)
-    try:
-        _alex_f16_case(ops, img, w, b, fs, scale, bias, psum, B)
-    finally:
-        ops.load().set_astem_f16_two_wg(True)
-
-
-def _alex_f16_case(ops, img, w, b, fs, scale, bias, psum, B):
-    from idunno.models.reference import preprocess_u8
-
-    y = ops.alex_stem_u8_f16(img, fs, bias, psum, scale)
+    y = ops.alex_stem_u8_f16(img, fs, bias, psum, scale, form=form)
     x = preprocess_u8(img)
     ref = F.max_pool2d(F.relu(F.conv2d(x, w.to(DEV), b.to(DEV), 4, 2)), 3, 2, 0).permute(0, 2, 3, 1)
     assert y.dtype == torch.float16 and y.shape == ref.shape
     _check(y, ref)
     big = torch.cat([img.flip(0), img])
     st = torch.tensor([B + 3], dtype=torch.long, device=DEV)
-    assert torch.equal(ops.alex_stem_u8_f16(big, fs, bias, psum, scale, st, B, 3), y)
+    assert torch.equal(ops.alex_stem_u8_f16(big, fs, bias, psum, scale, st, B, 3, form=form), y)
+    if (B, H, W) == (1, 31, 23):      # form -1 is today's default, two one-half workgroups per CU
+        assert torch.equal(ops.alex_stem_u8_f16(img, fs, bias, psum, scale, form=-1),
+                           ops.alex_stem_u8_f16(img, fs, bias, psum, scale, form=0))
+
+
+def test_no_process_global_kernel_switches(ops):
+    """Kernel form is a call argument: the extension exports no A/B setter."""
+    ext = ops.load()
+    # the only setter is the per-thread split range guard (thread_local, no kernel choice)
+    assert [n for n in dir(ext) if n.startswith("set_")] == ["set_split_guard"]
+    for switch in ("astem_ahead", "astem_phased", "astem_variant", "astem_f16_two_wg", "stem_prewait"):
+        assert not hasattr(ext, f"set_{switch}"), switch
 
 
 def test_runner_fused_stem_matches_unfused(ops):

@@ -425,22 +425,12 @@ def test_stem_split_fused(ops, B, hw):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", [0, 64])
+@pytest.mark.parametrize("form", [0, 1])
 @pytest.mark.parametrize("B,H,W", [(3, 224, 224), (2, 100, 131), (1, 31, 23), (5, 64, 72)])
-def test_alex_stem_split_fused(ops, B, H, W, variant):
+def test_alex_stem_split_fused(ops, B, H, W, form):
     """uint8 -> normalise -> conv11x11/4 pad 2 -> +bias -> ReLU -> maxpool3x3/2, split
     out, in one kernel (alex_stem.hip); ragged tiles and image borders included.
-    variant: the kernel form (set_astem_variant; 0 one half per CU, 64 phased halves)."""
-    from idunno.models import reference as ref
-
-    ops.load().set_astem_variant(variant)
-    try:
-        _alex_stem_check(ops, B, H, W)
-    finally:
-        ops.load().set_astem_variant(64)
-
-
-def _alex_stem_check(ops, B, H, W):
+    form: the kernel form, a call argument (0 one half per CU, 1 phased halves = the default)."""
     from idunno.models import reference as ref
 
     torch.manual_seed(B + H)
@@ -448,7 +438,7 @@ def _alex_stem_check(ops, B, H, W):
     w = torch.randn(64, 3, 11, 11) / (3 * 121) ** 0.5
     b = torch.randn(64) * 0.1
     fs, scale, bias, psum = P.pack_alex_stem_split(w, b)
-    y = ops.alex_stem_split(img, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale)
+    y = ops.alex_stem_split(img, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale, form=form)
     x = ref.preprocess_u8(img).permute(0, 2, 3, 1)
     want = _ref64(x, w, b, 4, 2, True).permute(0, 3, 1, 2)
     want = F.max_pool2d(want, 3, 2, 0).permute(0, 2, 3, 1)
@@ -457,9 +447,12 @@ def _alex_stem_check(ops, B, H, W):
     # device-side window of an HBM-resident shard: rows start - offset .. + batch
     big = torch.cat([img, img.flip(0)])
     start = torch.tensor([B + 5], dtype=torch.long, device=DEV)
-    y2 = ops.alex_stem_split(big, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale, start, B, 5)
+    y2 = ops.alex_stem_split(big, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale, start, B, 5, form=form)
     assert torch.equal(y2, ops.alex_stem_split(img.flip(0).contiguous(), fs.to(DEV), bias.to(DEV),
-                                               psum.to(DEV), scale))
+                                               psum.to(DEV), scale, form=form))
+    if (B, H, W) == (1, 31, 23):      # form -1 is today's default, the phased kernel
+        assert torch.equal(ops.alex_stem_split(img, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale, form=-1),
+                           ops.alex_stem_split(img, fs.to(DEV), bias.to(DEV), psum.to(DEV), scale, form=1))
 
 
 @pytest.mark.gpu

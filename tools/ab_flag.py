@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Same-process A/B of a runtime kernel switch of the extension: the whole
-forward hipGraph is captured once with ``<setter>(False)`` and once with
-``<setter>(True)`` (the flag is read at launch, so each graph keeps its
-setting), then the two graphs are timed in interleaved rounds on one device
-(cdna_hip_programming §5.4 rule 24).
+"""Same-process A/B of a HipRunner attribute (kernel choice is a call argument
+the runner passes, never a process-global switch): the whole forward hipGraph
+is captured once per value (the attribute is read at capture, so each graph
+keeps its setting), then the two graphs are timed in interleaved rounds on one
+device (cdna_hip_programming §5.4 rule 24).
 
-usage: python tools/ab_flag.py set_conv_stagger [--model resnet18] [--batch 400] [--dtype fp32]
-       python tools/ab_flag.py --attr side_down        (a HipRunner attribute instead)
+usage: python tools/ab_flag.py --attr side_down [--model resnet18] [--batch 400] [--dtype fp32]
+       python tools/ab_flag.py --attr astem_form --values 0,1 --model alexnet --batch 500
 """
 import argparse
 import os
@@ -20,10 +20,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("setter", nargs="?", default=None)
-    ap.add_argument("--attr", default=None, help="HipRunner attribute to switch instead of an extension setter")
+    ap.add_argument("--attr", required=True, help="HipRunner attribute to switch")
     ap.add_argument("--dtype", default="fp32")
-    ap.add_argument("--values", default=None, help="with --attr: 'a,b' integer values instead of False,True")
+    ap.add_argument("--values", default=None, help="'a,b' integer values instead of False,True")
     ap.add_argument("--model", default="resnet18")
     ap.add_argument("--batch", type=int, default=400)
     ap.add_argument("--iters", type=int, default=30)
@@ -32,29 +31,26 @@ def main():
     from idunno import ops
     from idunno.models import HipRunner, build_program
 
-    ext = ops.load()
-    setter = getattr(ext, a.setter) if a.setter else (lambda flag: None)
+    ops.load()
     dev = torch.device("cuda")
     prog = build_program(a.model, dtype=a.dtype)
     shard = ops.synth_images(1234, 0, a.batch, dev)
     runs, outs, keep = {}, {}, []
     vals = (False, True) if not a.values else tuple(int(v) for v in a.values.split(","))
     for flag in vals:
-        setter(flag)
         r = HipRunner(prog, dev)
-        if a.attr:
-            setattr(r, a.attr, flag)
+        assert hasattr(r, a.attr), f"HipRunner has no attribute {a.attr!r}"
+        setattr(r, a.attr, flag)
         keep.append(r)
         _start, run = r.capture_window(shard, a.batch)
         runs[flag] = run
         cls, prob = run()
         torch.cuda.synchronize()
         outs[flag] = (cls.clone(), prob.clone())
-    setter(False)
     v0, v1 = vals
     agree = (outs[v0][0] == outs[v1][0]).float().mean().item()
     dprob = (outs[v0][1] - outs[v1][1]).abs().max().item()
-    print(f"{a.setter or a.attr}: top-1 agreement off vs on {agree:.4f}, max |dprob| {dprob:.2e}", flush=True)
+    print(f"{a.attr}: top-1 agreement off vs on {agree:.4f}, max |dprob| {dprob:.2e}", flush=True)
     res = {k: [] for k in runs}
     for _ in range(a.rounds):
         for flag, run in runs.items():
@@ -68,7 +64,7 @@ def main():
             torch.cuda.synchronize()
             res[flag].append(t0.elapsed_time(t1) / a.iters)
     for flag, v in res.items():
-        print(f"{a.setter or a.attr}({flag!s:5s}) {a.model} b{a.batch}: median {statistics.median(v):.4f} ms  "
+        print(f"{a.attr}({flag!s:5s}) {a.model} b{a.batch}: median {statistics.median(v):.4f} ms  "
               f"min {min(v):.4f} ms  rounds {[round(x, 4) for x in v]}", flush=True)
     off, on = statistics.median(res[v0]), statistics.median(res[v1])
     print(f"on vs off: {100 * (off / on - 1):+.2f}% throughput", flush=True)

@@ -76,7 +76,7 @@ def probe(world: int, rounds: int) -> float:
     plane.node, plane.cfg = node, node.cfg
     plane.group = _Group(world, 512)
     plane.rounds_done = 0
-    plane.host_s = plane.host_cpu_s = plane.host_wait_s = 0.0
+    plane.host_s = plane.host_cpu_s = plane.host_wait_s = plane.host_release_s = 0.0
     plane._mirror_q = None
     t_total = 0.0
     for q in range(rounds):
