@@ -258,10 +258,16 @@ struct JpegHuffPacked {
   torch::Tensor hdr;                 // uint8 [n, sizeof(JpegHeader)]
   torch::Tensor bytes, sets, desc;   // uint8: entropy-coded bytes, JpegHuffSet[], JpegHuffDesc[n]
   int64_t n = 0, n_gpu = 0, nsets = 0, byte_total = 0, coef_total = 0;
+  // packed for the sub-stream kernel (jpeg_huff_par.h): JpegParDesc[n], the entries it takes (gpu == 2),
+  // those left to the one-lane kernel (restart markers) and the uint32 elements of scratch it needs
+  bool parallel = false;
+  torch::Tensor par;
+  int64_t n_par = 0, n_lane = 0, scratch_total = 0;
 };
 
-// Parses a list of bytes / None and packs the accepted entries, GIL released.
-std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas) {
+// Parses a list of bytes / None and packs the accepted entries, GIL released.  parallel: lay the
+// entries without restart markers out for the sub-stream kernel (jpeg_entropy_gpu_parallel).
+std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel) {
   const int n = (int)datas.size();
   std::vector<const uint8_t*> ptr(n, nullptr);
   std::vector<size_t> len(n, 0);
@@ -277,13 +283,20 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas) {
   JpegHuffBatch b;
   {
     py::gil_scoped_release nogil;
-    jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b);
+    jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b,
+                   parallel ? kJpegParSubBits : 0u);
   }
-  const char* why = jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total);
+  const char* why = parallel ? jpeg_huff_par_check(b.desc.data(), b.par.data(), n, b.byte_total, (int64_t)b.sets.size(),
+                                                   b.coef_total, b.scratch_total, kJpegParSubBits)
+                             : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total);
   TORCH_CHECK(why == nullptr, "jpeg_huff_pack: bad descriptor: ", why ? why : "");
   pk->bytes = torch::empty({b.byte_total}, torch::kUInt8);
   pk->sets = torch::empty({(int64_t)(b.sets.size() * sizeof(JpegHuffSet))}, torch::kUInt8);
   pk->desc = torch::empty({(int64_t)(b.desc.size() * sizeof(JpegHuffDesc))}, torch::kUInt8);
+  pk->parallel = parallel;
+  pk->par = torch::empty({(int64_t)(b.par.size() * sizeof(JpegParDesc))}, torch::kUInt8);
+  if (!b.par.empty()) std::memcpy(pk->par.data_ptr(), b.par.data(), b.par.size() * sizeof(JpegParDesc));
+  pk->scratch_total = b.scratch_total;
   {
     py::gil_scoped_release nogil;
     if (b.byte_total) jpeg_huff_copy_bytes(b, ptr.data(), len.data(), pk->bytes.data_ptr<uint8_t>());
@@ -296,6 +309,7 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas) {
     if (b.desc[i].gpu) {
       pk->offs[i] = b.desc[i].coef_base;
       ++pk->n_gpu;
+      ++(b.desc[i].gpu == 2 ? pk->n_par : pk->n_lane);
     }
   pk->nsets = (int64_t)b.sets.size();
   pk->byte_total = b.byte_total;
@@ -303,20 +317,28 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas) {
   return pk;
 }
 
-// Zeroes coefs and decodes the packed batch into it on the current stream: bytes uint8 (the
-// packed bytes, on the device), coefs int16 [>= coef_total], status int32 [n] (written for the
-// accepted entries only).  Every descriptor is checked against these very buffers first.
-void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
-                      torch::Tensor status) {
-  TORCH_CHECK(pk != nullptr, "no packed batch");
-  if (pk->n_gpu == 0) return;
+// The operand checks the two entropy launches share: bytes uint8 (the packed bytes, on the
+// device), coefs int16 [>= coef_total], status int32 [n], and the packed batch unchanged.
+static void check_entropy_operands(const char* op, const std::shared_ptr<JpegHuffPacked>& pk, const torch::Tensor& bytes,
+                                   const torch::Tensor& coefs, const torch::Tensor& status) {
   check_operand(bytes, "bytes", torch::kUInt8, -1, bytes.device());
   check_operand(coefs, "coefs", torch::kInt16, -1, bytes.device());
   check_operand(status, "status", torch::kInt32, -1, bytes.device());
-  TORCH_CHECK(status.numel() >= pk->n && pk->n < (1ll << 31), "jpeg_entropy_gpu: status buffer too small");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(bytes.data_ptr()) % 16 == 0, "jpeg_entropy_gpu: bytes must be 16-byte aligned");
+  TORCH_CHECK(status.numel() >= pk->n && pk->n < (1ll << 31), op, ": status buffer too small");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bytes.data_ptr()) % 16 == 0, op, ": bytes must be 16-byte aligned");
   TORCH_CHECK(pk->desc.numel() == pk->n * (int64_t)sizeof(JpegHuffDesc) &&
-                  pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet), "jpeg_entropy_gpu: packed batch changed");
+                  pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet), op, ": packed batch changed");
+}
+
+// Decodes the packed batch into coefs (zeroed by the caller: jpeg_entropy_zero) on the current
+// stream; status is written for the accepted entries only.  Every descriptor is checked against
+// these very buffers first.
+void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
+                      torch::Tensor status) {
+  TORCH_CHECK(pk != nullptr, "no packed batch");
+  TORCH_CHECK(!pk->parallel, "jpeg_entropy_gpu: the batch was packed for jpeg_entropy_gpu_parallel");
+  if (pk->n_gpu == 0) return;
+  check_entropy_operands("jpeg_entropy_gpu", pk, bytes, coefs, status);
   const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
                                     bytes.numel(), pk->nsets, coefs.numel());
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
@@ -326,6 +348,85 @@ void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor b
                       reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), coefs.data_ptr<int16_t>(),
                       status.data_ptr<int>(), (int)pk->n, cur_stream());
   check_launch("jpeg_entropy");
+}
+
+// The same for a batch packed with parallel = true: the sub-stream kernel on the entries laid out
+// for it, the one-lane kernel on the rest (restart markers), both into the same coefs / status.
+// scratch int32 [>= scratch_total]: the sub-stream state of the images too long for LDS.
+void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
+                               torch::Tensor status, torch::Tensor scratch) {
+  TORCH_CHECK(pk != nullptr, "no packed batch");
+  TORCH_CHECK(pk->parallel, "jpeg_entropy_gpu_parallel: the batch was packed for jpeg_entropy_gpu");
+  if (pk->n_gpu == 0) return;
+  check_entropy_operands("jpeg_entropy_gpu_parallel", pk, bytes, coefs, status);
+  check_operand(scratch, "scratch", torch::kInt32, -1, bytes.device());
+  TORCH_CHECK(pk->par.numel() == pk->n * (int64_t)sizeof(JpegParDesc), "jpeg_entropy_gpu_parallel: packed batch changed");
+  const char* why = jpeg_huff_par_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()),
+                                        reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n,
+                                        bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits);
+  TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu_parallel: descriptor outside its buffer: ", why ? why : "");
+  auto dev_desc = pk->desc.to(bytes.device());
+  auto dev_sets = pk->sets.to(bytes.device());
+  auto dev_par = pk->par.to(bytes.device());
+  const auto* sp = reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr());
+  const auto* dp = reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr());
+  if (pk->n_lane) {
+    jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), sp, dp, coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
+                        (int)pk->n, cur_stream());
+    check_launch("jpeg_entropy");
+  }
+  if (pk->n_par) {
+    jpeg_entropy_par_launch(bytes.data_ptr<uint8_t>(), sp, dp, reinterpret_cast<const JpegParDesc*>(dev_par.data_ptr()),
+                            coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
+                            reinterpret_cast<uint32_t*>(scratch.data_ptr<int>()), (int)pk->n, cur_stream());
+    check_launch("jpeg_entropy_par");
+  }
+}
+
+// Measurement helper (tools/jpeg_bench.py): the synchronisation rounds the sub-stream kernel needs for
+// each entry, found by running the rounds of jpeg_huff_par.h on the host with one virtual thread at the
+// kernel's sub-stream size and cap.  -1: not an entry that kernel takes; 0: not converged within the cap.
+std::vector<int64_t> jpeg_huff_par_rounds(py::list datas) {
+  const int n = (int)datas.size();
+  std::vector<const uint8_t*> ptr(n, nullptr);
+  std::vector<size_t> len(n, 0);
+  for (int i = 0; i < n; ++i) {
+    py::handle o = datas[i];
+    if (!o.is_none()) bytes_span(o, &ptr[i], &len[i]);
+    if (ptr[i] != nullptr && len[i] == 0) ptr[i] = nullptr;
+  }
+  std::vector<int64_t> rounds(n, -1);
+  py::gil_scoped_release nogil;
+  std::vector<JpegHeader> hdr((size_t)n);
+  std::vector<int> status(n, JPEG_EMPTY);
+  JpegHuffBatch b;
+  jpeg_huff_plan(n, ptr.data(), len.data(), hdr.data(), status.data(), &b, kJpegParSubBits);
+  std::vector<uint8_t> bytes((size_t)b.byte_total + 4);
+  jpeg_huff_copy_bytes(b, ptr.data(), len.data(), bytes.data());
+  std::vector<uint32_t> words(bytes.size() / 4);
+  std::memcpy(words.data(), bytes.data(), words.size() * 4);
+  std::vector<uint32_t> st;
+  for (int i = 0; i < n; ++i) {
+    const JpegHuffDesc& d = b.desc[(size_t)i];
+    if (d.gpu != 2) continue;
+    const JpegParDesc& p = b.par[(size_t)i];
+    const uint32_t nsub = jpeg_par_nsub(p.bit_len, kJpegParSubBits);
+    st.assign((size_t)kJpegParStateWords * nsub, 0u);
+    const JpegParCtx x{&d, &p, words.data() + d.byte_off / 4, &b.sets[(size_t)d.set_idx], st.data(), nullptr,
+                       kJpegParSubBits, nsub};
+    jpeg_par_init(x, 0, 1);
+    const uint32_t R = nsub < kJpegParMaxRounds ? nsub : kJpegParMaxRounds;
+    int cur = 0;
+    rounds[i] = 0;
+    for (uint32_t r = 0; r < R; ++r) {
+      if (!jpeg_par_round(x, cur, 0, 1)) {
+        rounds[i] = (int64_t)r + 1;
+        break;
+      }
+      cur ^= 1;
+    }
+  }
+  return rounds;
 }
 
 void jpeg_entropy_zero(torch::Tensor coefs) {
@@ -361,14 +462,29 @@ void bind_jpeg(py::module_& m) {
       .def_readonly("n_gpu", &JpegHuffPacked::n_gpu)
       .def_readonly("nsets", &JpegHuffPacked::nsets)
       .def_readonly("byte_total", &JpegHuffPacked::byte_total)
-      .def_readonly("coef_total", &JpegHuffPacked::coef_total);
+      .def_readonly("coef_total", &JpegHuffPacked::coef_total)
+      .def_readonly("parallel", &JpegHuffPacked::parallel)
+      .def_readonly("n_par", &JpegHuffPacked::n_par)
+      .def_readonly("n_lane", &JpegHuffPacked::n_lane)
+      .def_readonly("scratch_total", &JpegHuffPacked::scratch_total);
   m.def("jpeg_huff_pack", &jpeg_huff_pack,
-        "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage",
-        py::arg("datas"));
+        "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage "
+        "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel)",
+        py::arg("datas"), py::arg("parallel") = false);
+  m.attr("JPEG_PAR_SUB_BITS") = (int64_t)kJpegParSubBits;
+  m.attr("JPEG_PAR_THREADS") = (int64_t)kJpegParThreads;
+  m.attr("JPEG_PAR_MAX_ROUNDS") = (int64_t)kJpegParMaxRounds;
   m.def("jpeg_entropy_zero", &jpeg_entropy_zero, "async memset of a device coefficient buffer", py::arg("coefs"));
   m.def("jpeg_entropy_gpu", &jpeg_entropy_gpu,
         "Huffman-decode a packed batch on the device: one lane per image, int32 status per image",
         py::arg("packed"), py::arg("bytes"), py::arg("coefs"), py::arg("status"));
+  m.def("jpeg_entropy_gpu_parallel", &jpeg_entropy_gpu_parallel,
+        "Huffman-decode a batch packed with parallel=True: one workgroup per image on self-synchronising "
+        "sub-streams, restart-marker files on the one-lane kernel; status 100: not synchronised",
+        py::arg("packed"), py::arg("bytes"), py::arg("coefs"), py::arg("status"), py::arg("scratch"));
+  m.def("jpeg_huff_par_rounds", &jpeg_huff_par_rounds,
+        "synchronisation rounds the sub-stream kernel needs per entry, emulated on the host (-1: not its entry, "
+        "0: not within the cap)", py::arg("datas"));
   m.def("jpeg_idct", &jpeg_idct, "dequantise + 8x8 IDCT of a planned batch into uint8 component planes",
         py::arg("plan"), py::arg("coefs"), py::arg("planes"));
   m.def("jpeg_resize_crop", &jpeg_resize_crop,

@@ -154,7 +154,9 @@ struct Bits {
 };
 
 // a Huffman symbol, or -1 on a code the table does not hold; needs >= 16 bits in acc
-JH_HD inline int symbol(Bits& br, const JpegHuffTab& t) {
+// (B: Bits, or the plain-index reader of jpeg_huff_par.h)
+template <class B>
+JH_HD inline int symbol(B& br, const JpegHuffTab& t) {
   const unsigned e = t.look[br.peek(kJpegHuffLookBits)];
   if (e) {
     br.skip((int)(e >> 8));
@@ -175,7 +177,8 @@ JH_HD inline int symbol(Bits& br, const JpegHuffTab& t) {
 }
 
 // s in 1..15 magnitude bits -> signed value
-JH_HD inline int extend(Bits& br, int s) {
+template <class B>
+JH_HD inline int extend(B& br, int s) {
   const int v = (int)br.peek(s);
   br.skip(s);
   return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;

@@ -285,5 +285,12 @@ void jpeg_entropy_zero_launch(int16_t* coef, long long coef_elems, hipStream_t s
 // has run jpeg_huff_check (runtime/jpeg_huff_pack.h) over desc against the three buffers.
 void jpeg_entropy_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc, int16_t* coef,
                          int* status, int n, hipStream_t st);
+// one workgroup per entry of desc[0, n) on self-synchronising sub-streams (jpeg_huff_par.h); status[i] is
+// written for the entries with gpu == 2.  scratch: the uint32 state spans JpegParDesc::scratch_off names.
+// The caller has run jpeg_huff_par_check over desc and par against the four buffers.
+struct JpegParDesc;
+void jpeg_entropy_par_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
+                             const JpegParDesc* par, int16_t* coef, int* status, uint32_t* scratch, int n,
+                             hipStream_t st);
 
 }  // namespace idunno

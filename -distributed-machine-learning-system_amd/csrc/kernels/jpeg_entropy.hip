@@ -1,7 +1,8 @@
 // Device entropy stage of the JPEG source: Huffman streams -> quantised DCT
 // coefficients, the opt-in counterpart of runtime/jpeg_entropy.cpp.
 //
-// Huffman decoding is serial per stream, so the parallelism is over images: one
+// Two kernels.  jpeg_entropy_kernel (entropy_on="gpu"): Huffman decoding is serial
+// per stream, so the parallelism is over images: one
 // lane decodes one whole scan with the host/device core of jpeg_huff_core.h.
 // Workgroups are a single wave, so that a batch of B images spreads over
 // ceil(B / 64) CUs instead of filling a few.  The lanes of a wave walk different
@@ -12,12 +13,16 @@
 // would not fit the LDS of one wave's workgroup).  Coefficient stores are scattered
 // int16 writes into a buffer the launcher zeroed.
 //
-// The host (bindings.cpp jpeg_entropy_gpu) has checked every descriptor against
+// jpeg_entropy_par_kernel (entropy_on="gpu_parallel", further down) decodes one
+// image on a whole workgroup instead.
+//
+// The host (bind_jpeg.cpp jpeg_entropy_gpu / jpeg_entropy_gpu_parallel) has checked every descriptor against
 // the three buffers with jpeg_huff_check before the launch; inside a span the
 // core checks every access itself.
 #include <hip/hip_runtime.h>
 
 #include "../jpeg_huff_core.h"
+#include "../jpeg_huff_par.h"
 #include "../kernels.h"
 
 namespace idunno {
@@ -36,7 +41,98 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
                                     coef + d.coef_base);
 }
 
+// One image on the lanes of a whole workgroup (entropy_on="gpu_parallel"): the
+// self-synchronising sub-streams of jpeg_huff_par.h.  Workgroup i takes entry i of
+// the batch (gpu == 2; any other entry ends it at once); thread t takes the
+// sub-streams t, t + T, ... of kJpegParSubBits bits, so any stream length runs on
+// the fixed T = kJpegParThreads.  Everything the threads of an image exchange goes
+// through a barrier of their own workgroup: no workgroup waits for another one.
+//   * The image's table set (11.6 KB) is copied to LDS once: a lane step is a chain
+//     of dependent table lookups, and unlike the one-lane kernel all lanes of the
+//     workgroup share one set.
+//   * The state (6 words per sub-stream: two entry buffers, so that a round reads
+//     only what the previous round wrote, blocks completed, three DC sums) lives in
+//     LDS up to kParLdsSubs sub-streams (128 KiB of scan data), else in the image's
+//     span of the global scratch buffer.
+//   * Rounds: at most min(sub-streams, kJpegParMaxRounds); __syncthreads_or carries
+//     "some entry changed".  A lane step is divergent by nature (each lane walks its
+//     own bits); a lane whose entry did not change skips its step, so from the
+//     second round on most lanes of a wave are idle and the few that run finish
+//     sooner than a full pass.  Not converged: kJpegHuffUnsynced, nothing written.
+//   * Prefix of blocks and DC sums: each thread sums a contiguous share, reads the
+//     shares before its own from LDS, and rewrites its share as exclusive prefixes.
+//   * Write pass: strict decode with every store checked; any refusal, or a stream
+//     that ends before the scan's last block, is JPEG_CORRUPT.
+constexpr uint32_t kParLdsSubs = 1024;
+
+__global__ __launch_bounds__(kJpegParThreads) void jpeg_entropy_par_kernel(
+    const uint8_t* __restrict__ bytes, const JpegHuffSet* __restrict__ sets, const JpegHuffDesc* __restrict__ desc,
+    const JpegParDesc* __restrict__ par, int16_t* __restrict__ coef, int* __restrict__ status,
+    uint32_t* __restrict__ scratch, int n) {
+  __shared__ JpegHuffSet set_lds;
+  __shared__ uint32_t st_lds[kJpegParStateWords * kParLdsSubs];
+  __shared__ uint32_t part[kJpegParThreads][4];
+  const int i = (int)blockIdx.x;
+  if (i >= n) return;
+  const JpegHuffDesc& d = desc[i];
+  if (d.gpu != 2) return;                        // uniform: the whole workgroup leaves
+  const JpegParDesc& p = par[i];
+  const uint32_t t = threadIdx.x, T = kJpegParThreads;
+  {
+    static_assert(sizeof(JpegHuffSet) % 4 == 0, "copied by words");
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&sets[d.set_idx]);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&set_lds);
+    for (uint32_t q = t; q < sizeof(JpegHuffSet) / 4; q += T) dst[q] = src[q];
+  }
+  JpegParCtx x;
+  x.d = &d;
+  x.p = &p;
+  x.words = reinterpret_cast<const uint32_t*>(bytes + d.byte_off);
+  x.set = &set_lds;
+  x.sub_bits = kJpegParSubBits;
+  x.nsub = jpeg_par_nsub(p.bit_len, kJpegParSubBits);
+  x.st = x.nsub <= kParLdsSubs ? st_lds : scratch + p.scratch_off;
+  x.coef = coef + d.coef_base;
+  jpeg_par_init(x, t, T);
+  __syncthreads();
+  const uint32_t R = x.nsub < kJpegParMaxRounds ? x.nsub : kJpegParMaxRounds;
+  int cur = 0;
+  bool converged = false;
+  for (uint32_t r = 0; r < R; ++r) {
+    const bool any = jpeg_par_round(x, cur, t, T);
+    if (!__syncthreads_or(any ? 1 : 0)) {        // also the barrier between this round's writes and the next one's reads
+      converged = true;
+      break;
+    }
+    cur ^= 1;
+  }
+  if (!converged) {
+    if (t == 0) status[i] = kJpegHuffUnsynced;
+    return;
+  }
+  jpeg_par_partial(x, t, T, part[t]);
+  __syncthreads();
+  uint32_t base[4] = {0u, 0u, 0u, 0u};
+  for (uint32_t u = 0; u < t; ++u)
+    for (int q = 0; q < 4; ++q) base[q] += part[u][q];
+  jpeg_par_scan(x, t, T, base);
+  // the last thread's base + its own share: the blocks the whole stream holds
+  int bad = (t == T - 1 && base[0] + part[t][0] < p.total_blocks) ? 1 : 0;
+  __syncthreads();
+  if (jpeg_par_write(x, cur, t, T) != kJpegHuffOk) bad = 1;
+  bad = __syncthreads_or(bad);
+  if (t == 0) status[i] = bad ? kJpegHuffCorrupt : kJpegHuffOk;
+}
+
 }  // namespace
+
+void jpeg_entropy_par_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
+                             const JpegParDesc* par, int16_t* coef, int* status, uint32_t* scratch, int n,
+                             hipStream_t st) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(jpeg_entropy_par_kernel, dim3((unsigned)n), dim3(kJpegParThreads), 0, st, bytes, sets, desc, par,
+                     coef, status, scratch, n);
+}
 
 void jpeg_entropy_zero_launch(int16_t* coef, long long coef_elems, hipStream_t st) {
   if (coef_elems <= 0) return;

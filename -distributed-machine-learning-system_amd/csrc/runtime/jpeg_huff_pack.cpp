@@ -112,13 +112,41 @@ std::string set_key(const RawSet& rs) {
 
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
+// The data bytes of src[0, n) as jpeg_huff_detail::Bits::fill yields them, up to the
+// first marker, a lone trailing FF or the end; returns their number.  dst (or
+// nullptr: count only) receives byte i at (i & ~3) | (3 - (i & 3)): words whose most
+// significant byte comes first; never more than cap bytes.
+size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
+  size_t p = 0, k = 0;
+  while (p < n && k < cap) {
+    unsigned b = src[p];
+    if (b != 0xFFu) {
+      ++p;
+    } else if (p + 1 >= n) {
+      break;
+    } else if (src[p + 1] == 0xFFu) {
+      ++p;                          // fill byte: look again from the next FF
+      continue;
+    } else if (src[p + 1] == 0x00u) {
+      p += 2;
+    } else {
+      break;                        // a marker
+    }
+    if (dst != nullptr) dst[(k & ~(size_t)3) | (3u - (k & 3u))] = (uint8_t)b;
+    ++k;
+  }
+  return k;
+}
+
 }  // namespace
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out) {
+                    JpegHuffBatch* out, uint32_t par_sub_bits) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
-  out->byte_total = out->coef_total = 0;
+  out->byte_total = out->coef_total = out->scratch_total = 0;
+  out->par.clear();
+  if (par_sub_bits) out->par.assign((size_t)n, JpegParDesc{});
   std::map<std::string, int> seen;
   std::vector<RawSet> rsv(1);                 // ~2 KB: off the stack
   for (int i = 0; i < n; ++i) {
@@ -154,6 +182,21 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
     d.set_idx = it->second;
     d.byte_off = out->byte_total;
     d.byte_len = (uint32_t)(len[i] - h.scan_pos);
+    if (par_sub_bits && h.restart_interval == 0) {
+      const size_t k = destuff(data[i] + h.scan_pos, len[i] - h.scan_pos, nullptr, (size_t)-1);
+      if (k < kJpegParMaxBits / 8u) {
+        JpegParDesc& p = out->par[(size_t)i];
+        d.gpu = 2;
+        d.byte_len = (uint32_t)k;
+        p.bit_len = (uint32_t)k * 8u;
+        p.bpm = 0;
+        for (int c = 0; c < h.ncomp; ++c) p.bpm += h.comp[c].h * h.comp[c].v;
+        p.total_blocks = (uint32_t)h.mcux * (uint32_t)h.mcuy * (uint32_t)p.bpm;
+        p.scan_pos = h.scan_pos;
+        p.scratch_off = out->scratch_total;
+        out->scratch_total += (int64_t)kJpegParStateWords * jpeg_par_nsub(p.bit_len, par_sub_bits);
+      }
+    }
     d.byte_span = (uint32_t)round_up(d.byte_len, kJpegHuffBytePad);
     out->byte_total = round_up(d.byte_off + d.byte_span, kJpegHuffByteAlign);
     d.coef_base = out->coef_total;
@@ -181,18 +224,31 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
     const JpegHuffDesc& d = b.desc[i];
     if (!d.gpu) continue;
     if (d.byte_off > at) std::memset(dst + at, 0, (size_t)(d.byte_off - at));
+    if (d.gpu == 2) {
+      // the span was sized by the same walk over the same bytes
+      if (d.byte_span) std::memset(dst + d.byte_off, 0, d.byte_span);
+      const size_t scan = b.par[i].scan_pos < len[i] ? b.par[i].scan_pos : len[i];
+      if (d.byte_len) destuff(data[i] + scan, len[i] - scan, dst + d.byte_off, d.byte_len);
+      at = d.byte_off + d.byte_span;
+      continue;
+    }
     if (d.byte_len) std::memcpy(dst + d.byte_off, data[i] + (len[i] - d.byte_len), d.byte_len);
     at = d.byte_off + d.byte_len;
   }
   if (b.byte_total > at) std::memset(dst + at, 0, (size_t)(b.byte_total - at));
 }
 
-const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap) {
+namespace {
+
+const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
+                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
+  int64_t scratch_at = 0;
+  if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
   for (int i = 0; i < n; ++i) {
     const JpegHuffDesc& d = desc[i];
     if (!d.gpu) continue;
-    if (d.gpu != 1) return "gpu flag";
+    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr)) return "gpu flag";
     if (d.byte_off < byte_at || d.byte_off % kJpegHuffByteAlign != 0 || d.byte_len > d.byte_span ||
         d.byte_span % kJpegHuffBytePad != 0 || d.byte_off + (int64_t)d.byte_span > byte_cap)
       return "byte span outside the byte buffer";
@@ -213,8 +269,31 @@ const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, i
       co += (int64_t)d.bw[c] * d.bh[c] * 64;
     }
     if (co != (int64_t)d.total_coefs) return "coefficient count";
+    if (d.gpu == 2) {
+      const JpegParDesc& p = par[i];
+      int bpm = 0;
+      for (int c = 0; c < d.ncomp; ++c) bpm += d.h[c] * d.v[c];
+      if (d.restart_interval != 0 || d.byte_len >= kJpegParMaxBits / 8u || p.bit_len != d.byte_len * 8u ||
+          p.bpm != bpm || bpm > 63 || (int64_t)p.total_blocks != (int64_t)d.mcux * d.mcuy * bpm)
+        return "sub-stream descriptor";
+      const int64_t words = (int64_t)kJpegParStateWords * jpeg_par_nsub(p.bit_len, sub_bits);
+      if (p.scratch_off < scratch_at || p.scratch_off + words > scratch_cap) return "scratch span outside the scratch buffer";
+      scratch_at = p.scratch_off + words;
+    }
   }
   return nullptr;
+}
+
+}  // namespace
+
+const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0);
+}
+
+const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
+                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits) {
+  if (par == nullptr) return "no sub-stream descriptors";
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits);
 }
 
 }  // namespace idunno

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../jpeg_huff_core.h"
+#include "../jpeg_huff_par.h"
 #include "jpeg_entropy.h"
 
 namespace idunno {
@@ -21,16 +22,26 @@ struct JpegHuffBatch {
   std::vector<JpegHuffSet> sets;    // identical table sets share one entry
   int64_t byte_total = 0;           // bytes of the batch byte buffer
   int64_t coef_total = 0;           // int16 elements of the batch coefficient buffer
+  // the sub-stream form (jpeg_huff_plan with par_sub_bits != 0), else empty / 0
+  std::vector<JpegParDesc> par;     // one per entry, meaningful where desc[i].gpu == 2
+  int64_t scratch_total = 0;        // uint32 elements of the batch scratch buffer
 };
 
 // Parses every entry (data[i] == nullptr: JPEG_EMPTY) and lays the batch out.
 // status[i] and hdr[i] are what jpeg_parse_header gives; an accepted image gets
 // its byte span at an aligned offset and its coefficients after its predecessors'.
+// par_sub_bits != 0 (a multiple of 32, the sub-stream size of jpeg_huff_par.h) lays
+// the batch out for the sub-stream kernel as well: an accepted image without a
+// restart interval whose scan is shorter than kJpegParMaxBits gets gpu == 2, a byte
+// span sized for its de-stuffed words, a JpegParDesc and a scratch span; every
+// other accepted image keeps gpu == 1 and the stuffed layout of the one-lane kernel.
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out);
+                    JpegHuffBatch* out, uint32_t par_sub_bits = 0);
 
 // Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
-// zeroes the padding between them.
+// zeroes the padding between them.  A gpu == 2 entry gets its de-stuffed words
+// instead: FF 00 -> FF, fill bytes dropped, cut at the first marker (the rules of
+// jpeg_huff_detail::Bits::fill), four bytes per word, most significant first.
 void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, const size_t* len, uint8_t* dst);
 
 // Every descriptor against the three buffers it indexes (byte_cap bytes, nsets
@@ -38,5 +49,11 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 // and the layout inside each span is consistent, else what is wrong.  Run before
 // a launch.
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap);
+
+// The same for a batch planned with par_sub_bits: gpu == 1 entries as above, gpu == 2
+// entries also against their JpegParDesc and the scratch buffer (scratch_cap uint32
+// elements, kJpegParStateWords per sub-stream of sub_bits bits).
+const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
+                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits);
 
 }  // namespace idunno

@@ -65,11 +65,12 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     by index -- ``drop_gpu_sources()`` after replacing files; without a GPU it
     decodes with Pillow like ``"pil"``).  ``entropy_on="gpu"`` (with
     ``decoder="gpu"``) also decodes the Huffman streams on the device instead of
-    on host threads; the default is ``"host"``."""
+    on host threads, one lane per image, and ``"gpu_parallel"`` does so with one
+    workgroup per image; the default is ``"host"``."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
-    if entropy_on not in ("host", "gpu"):
-        raise ValueError(f"entropy_on must be 'host' or 'gpu', not {entropy_on!r}")
+    if entropy_on not in ("host", "gpu", "gpu_parallel"):
+        raise ValueError(f"entropy_on must be 'host', 'gpu' or 'gpu_parallel', not {entropy_on!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -108,8 +109,9 @@ def main(argv=None) -> int:
     ap.add_argument("--batch", type=int, default=0, help="images per forward (1 = reference behaviour)")
     ap.add_argument("--decoder", default="pil", choices=["pil", "gpu"],
                     help="JPEG decode: Pillow on host threads, or native entropy decode + HIP kernels")
-    ap.add_argument("--entropy", default="host", choices=["host", "gpu"],
-                    help="with --decoder gpu: Huffman decode on host threads, or on the device (one lane per image)")
+    ap.add_argument("--entropy", default="host", choices=["host", "gpu", "gpu_parallel"],
+                    help="with --decoder gpu: Huffman decode on host threads, on the device (one lane per image), "
+                         "or on the device with one workgroup per image")
     a = ap.parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
                            decoder=a.decoder, entropy_on=a.entropy)

@@ -131,8 +131,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--standby", type=int, default=None)
     ap.add_argument("--executor", default="auto", choices=["auto", "hip", "torch", "fake"])
     ap.add_argument("--source", default="synthetic", choices=["synthetic", "sdfs", "jpeg"])
-    ap.add_argument("--jpeg-entropy", default="host", choices=["host", "gpu"],
-                    help="--source jpeg: Huffman decode on host threads, or on the device (no decode threads)")
+    ap.add_argument("--jpeg-entropy", default="host", choices=["host", "gpu", "gpu_parallel"],
+                    help="--source jpeg: Huffman decode on host threads, or on the device (no decode threads): "
+                         "gpu = one lane per image, gpu_parallel = one workgroup per image")
     ap.add_argument("--shell", action="store_true")
     ap.add_argument("--shell-node", type=int, default=None)
     ap.add_argument("--no-shell", action="store_true")

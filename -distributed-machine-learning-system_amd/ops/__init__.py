@@ -15,7 +15,8 @@ __all__ = [
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
-    "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu",
+    "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
+    "JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS",
 ]
 
 
@@ -354,12 +355,23 @@ def jpeg_entropy_batch(datas, threads: int = 8):
     return load().jpeg_entropy_batch(datas, int(threads))
 
 
-def jpeg_huff_pack(datas):
+_JPEG_PAR_CONSTANTS = ("JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS")
+
+
+def __getattr__(name: str):
+    # the sub-stream kernel's constants (csrc/jpeg_huff_par.h): bits per sub-stream, threads per
+    # workgroup (= per image) and the cap on synchronisation rounds, read from the built library
+    if name in _JPEG_PAR_CONSTANTS:
+        return int(getattr(load(), name))
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def jpeg_huff_pack(datas, parallel: bool = False):
     """Parse a list of ``bytes | None`` and pack the accepted entries for the
     device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
     ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
     ``bytes`` (host uint8 tensor, ``byte_total``), ``coef_total``, ``n_gpu``."""
-    return load().jpeg_huff_pack(datas)
+    return load().jpeg_huff_pack(datas, bool(parallel))
 
 
 def jpeg_entropy_zero(coefs):
@@ -372,6 +384,24 @@ def jpeg_entropy_gpu(packed, dev_bytes, coefs, status):
     packed bytes in HBM -> int16 coefficients (zeroed by the caller), int32
     status per accepted entry.  Descriptors are checked against the buffers."""
     load().jpeg_entropy_gpu(packed, dev_bytes, coefs, status)
+
+
+def jpeg_entropy_gpu_parallel(packed, dev_bytes, coefs, status, scratch):
+    """The same for a batch packed with ``parallel=True``: one workgroup of
+    ``JPEG_PAR_THREADS`` threads per image on self-synchronising sub-streams of
+    ``JPEG_PAR_SUB_BITS`` bits; the entries with restart markers go to the
+    one-lane kernel in the same call.  ``scratch``: int32, at least
+    ``packed.scratch_total`` elements.  A status of 100 is an image whose
+    sub-streams had not synchronised after ``JPEG_PAR_MAX_ROUNDS`` rounds."""
+    load().jpeg_entropy_gpu_parallel(packed, dev_bytes, coefs, status, scratch)
+
+
+def jpeg_huff_par_rounds(datas):
+    """Measurement helper: the synchronisation rounds the sub-stream kernel
+    needs for each entry of a list of ``bytes | None``, found by running the
+    same rounds on the host (-1: an entry that kernel does not take, 0: not
+    converged within ``JPEG_PAR_MAX_ROUNDS``)."""
+    return load().jpeg_huff_par_rounds(datas)
 
 
 def jpeg_plan(hdr, status, offs, coef_elems: int, geom, crop: int, device):

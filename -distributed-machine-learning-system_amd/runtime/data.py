@@ -631,13 +631,19 @@ class GpuJpegSource:
     ``entropy_on="gpu"`` (opt-in, default ``"host"``) decodes the Huffman
     streams on the device too (kernels/jpeg_entropy.hip): the front thread then
     only parses and packs, no decode threads run, and chunks are ``CHUNK_GPU``
-    images."""
+    images.  ``entropy_on="gpu_parallel"`` (opt-in as well) decodes each image
+    on a whole workgroup (self-synchronising sub-streams, csrc/jpeg_huff_par.h);
+    its kernel time grows with the chunk instead of being one stream's latency
+    whatever the chunk holds, so it keeps the host form's chunk size,
+    ``CHUNK_GPU_PARALLEL`` = ``CHUNK`` (docs/KERNELS.md, "JPEG decode", has the
+    measurement)."""
 
     CHUNK = 256          # images per decode_batch call (bounds the coefficient buffers: ~0.6 MB per 500x375 image)
     # entropy_on="gpu": one lane decodes one image, so the entropy kernel's throughput is the chunk
     # size over one image's decode latency and it wants larger chunks than the host form.  The
     # coefficients of a chunk live in HBM: ~0.6 MB per 500x375 image, ~1.2 GB at 2048.
     CHUNK_GPU = 2048
+    CHUNK_GPU_PARALLEL = 256
 
     def __init__(self, device, root: str | None = None, sdfs=None, prefix: str = "", cache_bytes: int = 16 << 30,
                  threads: int = 8, resize: int = 256, crop: int = HW, entropy_on: str = "host"):
@@ -710,7 +716,9 @@ class GpuJpegSource:
             return datas, (jpeg.entropy_batch(datas, self.threads, self.entropy_on) if gpu else None)
 
         got, absent = {}, set()
-        chunk = self.CHUNK_GPU if gpu and self.entropy_on == "gpu" else self.CHUNK
+        chunk = self.CHUNK
+        if gpu and self.entropy_on != "host":
+            chunk = self.CHUNK_GPU if self.entropy_on == "gpu" else self.CHUNK_GPU_PARALLEL
         parts = [idx[c:c + chunk] for c in range(0, len(idx), chunk)]
         if self._front is None:
             from concurrent.futures import ThreadPoolExecutor

@@ -13,6 +13,12 @@ coefficients (an eighth of the size):
     bytes + tables + descriptors --(HbmStager)--> HBM --(kernels/jpeg_entropy.hip:
     memset, jpeg_entropy_kernel)--> int16 coefficients in HBM --> the same two kernels
 
+``entropy_on="gpu_parallel"`` (opt-in as well) decodes one image on the many
+lanes of a workgroup instead (self-synchronising sub-streams, csrc/jpeg_huff_par.h,
+jpeg_entropy_par_kernel), so a small query no longer waits for one lane to walk
+a whole stream; files with restart markers keep the one-lane kernel in the same
+batch.
+
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
 crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
@@ -182,7 +188,17 @@ def _stager(device: torch.device) -> HbmStager:
     return st
 
 
-ENTROPY_ON = ("host", "gpu")
+ENTROPY_ON = ("host", "gpu", "gpu_parallel")
+_DEVICE_FORMS = ("gpu", "gpu_parallel")
+_UNSYNCED = 100           # kJpegHuffUnsynced: the sub-stream kernel's rounds hit their cap (device-only status)
+
+
+def _refusal(C, data: bytes, status: int) -> str:
+    """Why an entry is a fallback: the parse's reason, else what the entropy stage said."""
+    st, reason, _ = C.jpeg_parse(data)
+    if st != 0:
+        return reason
+    return "unsynced" if status == _UNSYNCED else "corrupt"
 
 
 def _check_entropy_on(entropy_on: str) -> str:
@@ -195,15 +211,15 @@ def entropy_batch(datas, threads: int = 8, entropy_on: str = "host"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
-    kernels).  With ``entropy_on="gpu"`` it only parses the headers and packs
-    bytes, tables and descriptors for the entropy kernel (one thread, GIL
-    released as well).  Returns what ``decode_batch(..., entropy=)`` takes."""
+    kernels).  With ``entropy_on="gpu"`` or ``"gpu_parallel"`` it only parses the
+    headers and packs bytes, tables and descriptors for the entropy kernels (one
+    thread, GIL released as well).  Returns what ``decode_batch(..., entropy=)`` takes."""
     _check_entropy_on(entropy_on)
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
-    if entropy_on == "gpu":
-        packed = _C().jpeg_huff_pack(datas)
-        return "gpu", datas, packed, time.perf_counter() - t0
+    if entropy_on in _DEVICE_FORMS:
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel")
+        return entropy_on, datas, packed, time.perf_counter() - t0
     status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads))
     return datas, status, hdr, coefs, offs, time.perf_counter() - t0
 
@@ -224,7 +240,12 @@ def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
     dev_status = torch.zeros(packed.n, dtype=torch.int32, device=device)
     C.jpeg_entropy_zero(dev_coefs)
     ev[2].record(cur)
-    C.jpeg_entropy_gpu(packed, dev_bytes, dev_coefs, dev_status)
+    if packed.parallel:
+        # the rounds' per-sub-stream state of the images too long for LDS; no need to zero it
+        scratch = torch.empty(max(int(packed.scratch_total), 1), dtype=torch.int32, device=device)
+        C.jpeg_entropy_gpu_parallel(packed, dev_bytes, dev_coefs, dev_status, scratch)
+    else:
+        C.jpeg_entropy_gpu(packed, dev_bytes, dev_coefs, dev_status)
     ev[3].record(cur)
 
     def times():
@@ -238,8 +259,8 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
     """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
-    from the host decoder or, with ``entropy_on="gpu"`` on a GPU ``device``,
-    from the entropy kernel."""
+    from the host decoder or, with ``entropy_on="gpu"`` / ``"gpu_parallel"`` on a
+    GPU ``device``, from the entropy kernels."""
     _check_entropy_on(entropy_on)
     C = _C()
     datas = [None if d is None else bytes(d) for d in datas]
@@ -248,10 +269,10 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
         return list(status), list(offs), coefs
     device = torch.device(device)
     if device.type != "cuda":
-        raise ValueError("entropy_on='gpu' needs a GPU device")
+        raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas)
+    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel")
     status = list(packed.status)
     coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
     if packed.n_gpu:
@@ -286,18 +307,25 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     host's parse + pack (wall).  An image the kernel flags is a ``"corrupt"``
     fallback exactly like one the host decoder refuses.  ``info["entropy_on"]``
     names the form in effect (on a CPU device: the one asked for; nothing
-    native runs there)."""
+    native runs there).
+
+    ``entropy_on="gpu_parallel"`` is the same with one workgroup per image
+    (sub-streams that synchronise themselves, csrc/jpeg_huff_par.h); files with
+    restart markers take the one-lane kernel inside the same batch.  An image
+    whose sub-streams did not synchronise within the kernel's round cap is an
+    ``"unsynced"`` fallback."""
     _check_entropy_on(entropy_on)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
-    on_gpu = entropy_on == "gpu" if entropy is None else isinstance(entropy[0], str)
+    form = entropy_on if entropy is None else (entropy[0] if isinstance(entropy[0], str) else "host")
+    on_gpu = form in _DEVICE_FORMS
     if entropy is None:
         datas = [None if d is None else bytes(d) for d in datas]
     else:
         datas = entropy[1] if on_gpu else entropy[0]
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
-            "gpu_images": 0, "entropy_on": "gpu" if on_gpu else "host"}
+            "gpu_images": 0, "entropy_on": form}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -316,7 +344,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         device = torch.device("cuda", torch.cuda.current_device())
     packed = None
     if on_gpu:
-        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, "gpu")
+        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form)
         status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
     else:
         _, status, hdr, coefs, offs, info["entropy_s"] = entropy if entropy is not None else entropy_batch(datas, threads)
@@ -379,8 +407,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 imgs.append(None)
                 continue
             if status[i] != 0:
-                st, reason, _ = C.jpeg_parse(d)
-                info["fallbacks"].append((i, reason if st != 0 else "corrupt"))
+                info["fallbacks"].append((i, _refusal(C, d, status[i])))
                 t = torch.from_numpy(host(d).copy()).to(device)
                 if full:
                     imgs.append(t)

@@ -15,8 +15,15 @@ opt-in stage on the device (``entropy_on="gpu"``), cold passes alternating in
 the same process: host threads ``--threads`` and 2 (one rank's share when 8
 ranks split 16 CPUs), device form at each ``--gpu-chunks`` size; per pass
 images/s, entropy time, H2D bytes and time, and host CPU seconds
-(``time.process_time``: all threads of the process).  Needs a GPU: without one
-it exits with an error.
+(``time.process_time``: all threads of the process).  The sub-stream device
+form (``entropy_on="gpu_parallel"``, one workgroup per image) runs the same
+full passes at each ``--par-chunks`` size, and all four forms (host at
+``--threads`` and at 2, ``gpu``, ``gpu_parallel``) answer a small cold query of
+each ``--queries`` size (default 64 and 400 images: nothing resident, a fresh
+source per query), alternating in that same process after a warm-up of every
+form.  The synchronisation rounds the sub-stream kernel needs on these files are
+found on the host with the same code (``ops.jpeg_huff_par_rounds``).  Needs a
+GPU: without one it exits with an error.
 
     python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
 """
@@ -59,6 +66,8 @@ def main(argv=None) -> int:
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--gpu-chunks", default="256,1024,2048", help="GpuJpegSource.CHUNK_GPU values of the device entropy rows")
+    ap.add_argument("--par-chunks", default="64,256,1024", help="GpuJpegSource.CHUNK_GPU_PARALLEL values of the sub-stream rows")
+    ap.add_argument("--queries", default="64,400", help="sizes of the small cold queries")
     ap.add_argument("--entropy-only", action="store_true", help="only the host / device entropy comparison")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
@@ -141,11 +150,12 @@ def main(argv=None) -> int:
         # ---- entropy stage: host threads against the device kernel, same process, alternating ----
         forms = [(f"host, {a.threads} threads", "host", a.threads, None), ("host, 2 threads", "host", 2, None)]
         forms += [(f"gpu, chunk {c}", "gpu", a.threads, int(c)) for c in a.gpu_chunks.split(",") if c]
+        forms += [(f"gpu_parallel, chunk {c}", "gpu_parallel", a.threads, int(c)) for c in a.par_chunks.split(",") if c]
 
         def source(on, threads, chunk):
             src = GpuJpegSource(dev, root=d, threads=threads, entropy_on=on)
             if chunk is not None:
-                src.CHUNK_GPU = chunk
+                src.CHUNK_GPU = src.CHUNK_GPU_PARALLEL = chunk
             return src
 
         want = source("host", a.threads, None).get(0, n - 1)
@@ -168,15 +178,54 @@ def main(argv=None) -> int:
                 v["h2d_s"].append(src.seconds["h2d_s"])
                 v["h2d_b"].append(src.stager.bytes_staged)
                 v["cpu_s"].append(cpu)
-                say(f"entropy rep {r}: {name:18s} {n / dt:9.1f} img/s  entropy {1e3 * src.seconds['entropy_s']:8.2f} ms  "
+                say(f"entropy rep {r}: {name:24s} {n / dt:9.1f} img/s  entropy {1e3 * src.seconds['entropy_s']:8.2f} ms  "
                     f"H2D {src.stager.bytes_staged / 1e6:8.1f} MB in {1e3 * src.seconds['h2d_s']:7.2f} ms  host CPU {cpu:6.3f} s")
                 del y, src
         say("entropy stage, cold GpuJpegSource.get (entropy: host wall over the decode threads / device events of the kernel):")
         for name, *_ in forms:
             v = res[name]
-            say(f"  {name:18s} median {np.median(v['rate']):9.1f} img/s  min {min(v['rate']):9.1f}  max {max(v['rate']):9.1f} | "
-                f"entropy {1e3 * np.median(v['entropy_s']):8.2f} ms | H2D {np.median(v['h2d_b']) / 1e6:8.1f} MB "
-                f"{1e3 * np.median(v['h2d_s']):7.2f} ms | host CPU {np.median(v['cpu_s']):6.3f} s")
+            say(f"  {name:24s} median {np.median(v['rate']):9.1f} img/s  min {min(v['rate']):9.1f}  max {max(v['rate']):9.1f} | "
+                f"entropy {1e3 * np.median(v['entropy_s']):8.2f} ms ({1e6 * np.median(v['entropy_s']) / n:7.1f} us/image) | "
+                f"H2D {np.median(v['h2d_b']) / 1e6:8.1f} MB {1e3 * np.median(v['h2d_s']):7.2f} ms | "
+                f"host CPU {np.median(v['cpu_s']):6.3f} s")
+        # ---- small cold queries: a fresh source per query, default chunk sizes, forms alternating ----
+        qforms = [(f"host, {a.threads} threads", "host", a.threads), ("host, 2 threads", "host", 2),
+                  ("gpu", "gpu", a.threads), ("gpu_parallel", "gpu_parallel", a.threads)]
+        for q in [int(x) for x in a.queries.split(",") if x]:
+            q = min(q, n)
+            want = source("host", a.threads, None).get(0, q - 1)
+            for _, on, threads in qforms:                           # warm-up of every form at this size
+                assert torch.equal(source(on, threads, None).get(0, q - 1), want), (on, threads, q)
+            del want
+            qres = {name: {"ms": [], "entropy_ms": [], "cpu_s": []} for name, *_ in qforms}
+            for r in range(a.reps):
+                for name, on, threads in qforms:
+                    src = source(on, threads, None)
+                    c0 = time.process_time()
+                    dt, y = timed(lambda: src.get(0, q - 1))
+                    cpu = time.process_time() - c0
+                    assert src.decoded == q and src.fallbacks == 0
+                    qres[name]["ms"].append(1e3 * dt)
+                    qres[name]["entropy_ms"].append(1e3 * src.seconds["entropy_s"])
+                    qres[name]["cpu_s"].append(cpu)
+                    say(f"query {q} rep {r}: {name:18s} {1e3 * dt:9.2f} ms  entropy {1e3 * src.seconds['entropy_s']:8.2f} ms  "
+                        f"host CPU {cpu:6.3f} s")
+                    del y, src
+            say(f"cold query of {q} images, GpuJpegSource.get (wall; entropy: host wall / device events of the kernels):")
+            for name, *_ in qforms:
+                v = qres[name]
+                say(f"  {name:18s} median {np.median(v['ms']):9.2f} ms  min {min(v['ms']):9.2f}  max {max(v['ms']):9.2f} | "
+                    f"entropy {np.median(v['entropy_ms']):8.2f} ms ({1e3 * np.median(v['entropy_ms']) / q:7.1f} us/image) | "
+                    f"host CPU {np.median(v['cpu_s']):6.3f} s")
+            g, p_ = np.median(qres["gpu"]["ms"]), np.median(qres["gpu_parallel"]["ms"])
+            h = np.median(qres[qforms[0][0]]["ms"])
+            say(f"  gpu / gpu_parallel = {g / p_:.2f}x, host {a.threads} threads / gpu_parallel = {h / p_:.2f}x (medians)")
+        # ---- synchronisation rounds of the sub-stream kernel on these files (host emulation, same code) ----
+        datas = [open(os.path.join(d, f"test_{i}.JPEG"), "rb").read() for i in range(n)]
+        rounds = np.asarray(ops.jpeg_huff_par_rounds(datas))
+        say(f"sub-stream kernel: {ops.JPEG_PAR_SUB_BITS} bits per sub-stream, {ops.JPEG_PAR_THREADS} threads per image, "
+            f"round cap {ops.JPEG_PAR_MAX_ROUNDS}; rounds over {n} files: min {rounds.min()}  median {int(np.median(rounds))}  "
+            f"max {rounds.max()}  (0 = not converged: {int((rounds == 0).sum())} files)")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
