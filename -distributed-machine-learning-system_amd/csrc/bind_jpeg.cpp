@@ -16,6 +16,8 @@ static py::dict jpeg_header_dict(const JpegHeader& h) {
   d["mode"] = h.mode;
   d["restart_interval"] = h.restart_interval;
   d["total_coefs"] = (int64_t)h.total_coefs;
+  d["progressive"] = h.progressive != 0;
+  d["nscans"] = h.nscans;
   py::list comps;
   for (int c = 0; c < h.ncomp; ++c) {
     const JpegComp& cp = h.comp[c];
@@ -41,12 +43,13 @@ static void bytes_span(const py::handle& o, const uint8_t** p, size_t* n) {
 }
 
 // (status, reason, header dict or None)
-py::tuple jpeg_parse(py::bytes data) {
+// native_progressive: a progressive file of a supported layout is walked to EOI and accepted
+py::tuple jpeg_parse(py::bytes data, bool native_progressive) {
   const uint8_t* p;
   size_t n;
   bytes_span(data, &p, &n);
   JpegHeader h;
-  const int st = jpeg_parse_header(n ? p : nullptr, n, &h);
+  const int st = jpeg_parse_header(n ? p : nullptr, n, &h, native_progressive);
   return py::make_tuple(st, jpeg_status_name(st), st == JPEG_OK ? py::object(jpeg_header_dict(h)) : py::none());
 }
 
@@ -54,7 +57,8 @@ py::tuple jpeg_parse(py::bytes data) {
 // released.  Returns (status per entry, headers uint8 [n, sizeof(JpegHeader)],
 // coefficients int16 [total] on the host, first coefficient of each entry or -1).
 // Only entries whose header parses get room in the coefficient buffer.
-py::tuple jpeg_entropy_batch(py::list datas, int64_t threads) {
+// native_progressive: progressive files are decoded too (the core of jpeg_huff_prog.h).
+py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progressive) {
   const int n = (int)datas.size();
   TORCH_CHECK(threads >= 1 && threads <= 256, "threads out of range");
   std::vector<const uint8_t*> ptr(n, nullptr);
@@ -75,7 +79,7 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads) {
     py::gil_scoped_release nogil;
     for (int i = 0; i < n; ++i) {
       if (ptr[i] == nullptr) continue;
-      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i]);
+      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i], native_progressive);
       if (status[i] != JPEG_OK) {
         ptr[i] = nullptr;                    // keeps its parse status: not decoded
         continue;
@@ -94,7 +98,8 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads) {
     std::vector<int> st2(n, JPEG_EMPTY);
     std::vector<JpegHeader> h2((size_t)n);
     py::gil_scoped_release nogil;
-    jpeg_decode_batch(n, ptr.data(), len.data(), h2.data(), out.data(), cap.data(), st2.data(), (int)threads);
+    jpeg_decode_batch(n, ptr.data(), len.data(), h2.data(), out.data(), cap.data(), st2.data(), (int)threads,
+                      native_progressive);
     for (int i = 0; i < n; ++i)
       if (ptr[i] != nullptr) status[i] = st2[i];
   }
@@ -263,11 +268,17 @@ struct JpegHuffPacked {
   bool parallel = false;
   torch::Tensor par;
   int64_t n_par = 0, n_lane = 0, scratch_total = 0;
+  // packed with native_progressive: the progressive entries (gpu == 3) as JpegProgScan[nscans],
+  // JpegHuffTab[ntabs] and the int32 indices of those entries, for jpeg_entropy_prog_kernel
+  bool native_progressive = false;
+  torch::Tensor scans, tabs, prog_list;
+  int64_t n_prog = 0, nscans = 0, ntabs = 0;
 };
 
 // Parses a list of bytes / None and packs the accepted entries, GIL released.  parallel: lay the
 // entries without restart markers out for the sub-stream kernel (jpeg_entropy_gpu_parallel).
-std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel) {
+// native_progressive: progressive files are accepted and laid out for the progressive kernel.
+std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bool native_progressive) {
   const int n = (int)datas.size();
   std::vector<const uint8_t*> ptr(n, nullptr);
   std::vector<size_t> len(n, 0);
@@ -284,11 +295,14 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel) {
   {
     py::gil_scoped_release nogil;
     jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b,
-                   parallel ? kJpegParSubBits : 0u);
+                   parallel ? kJpegParSubBits : 0u, native_progressive);
   }
   const char* why = parallel ? jpeg_huff_par_check(b.desc.data(), b.par.data(), n, b.byte_total, (int64_t)b.sets.size(),
-                                                   b.coef_total, b.scratch_total, kJpegParSubBits)
-                             : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total);
+                                                   b.coef_total, b.scratch_total, kJpegParSubBits, native_progressive)
+                             : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total,
+                                               native_progressive);
+  if (why == nullptr && native_progressive)
+    why = jpeg_huff_prog_check(b.desc.data(), n, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   TORCH_CHECK(why == nullptr, "jpeg_huff_pack: bad descriptor: ", why ? why : "");
   pk->bytes = torch::empty({b.byte_total}, torch::kUInt8);
   pk->sets = torch::empty({(int64_t)(b.sets.size() * sizeof(JpegHuffSet))}, torch::kUInt8);
@@ -297,6 +311,14 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel) {
   pk->par = torch::empty({(int64_t)(b.par.size() * sizeof(JpegParDesc))}, torch::kUInt8);
   if (!b.par.empty()) std::memcpy(pk->par.data_ptr(), b.par.data(), b.par.size() * sizeof(JpegParDesc));
   pk->scratch_total = b.scratch_total;
+  pk->native_progressive = native_progressive;
+  pk->nscans = (int64_t)b.scans.size();
+  pk->ntabs = (int64_t)b.tabs.size();
+  pk->scans = torch::empty({(int64_t)(b.scans.size() * sizeof(JpegProgScan))}, torch::kUInt8);
+  pk->tabs = torch::empty({(int64_t)(b.tabs.size() * sizeof(JpegHuffTab))}, torch::kUInt8);
+  if (!b.scans.empty()) std::memcpy(pk->scans.data_ptr(), b.scans.data(), b.scans.size() * sizeof(JpegProgScan));
+  if (!b.tabs.empty()) std::memcpy(pk->tabs.data_ptr(), b.tabs.data(), b.tabs.size() * sizeof(JpegHuffTab));
+  std::vector<int32_t> prog_list;
   {
     py::gil_scoped_release nogil;
     if (b.byte_total) jpeg_huff_copy_bytes(b, ptr.data(), len.data(), pk->bytes.data_ptr<uint8_t>());
@@ -309,8 +331,12 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel) {
     if (b.desc[i].gpu) {
       pk->offs[i] = b.desc[i].coef_base;
       ++pk->n_gpu;
-      ++(b.desc[i].gpu == 2 ? pk->n_par : pk->n_lane);
+      if (b.desc[i].gpu == 3) prog_list.push_back(i);
+      else ++(b.desc[i].gpu == 2 ? pk->n_par : pk->n_lane);
     }
+  pk->n_prog = (int64_t)prog_list.size();
+  pk->prog_list = torch::empty({pk->n_prog}, torch::kInt32);
+  if (pk->n_prog) std::memcpy(pk->prog_list.data_ptr(), prog_list.data(), prog_list.size() * sizeof(int32_t));
   pk->nsets = (int64_t)b.sets.size();
   pk->byte_total = b.byte_total;
   pk->coef_total = b.coef_total;
@@ -327,7 +353,34 @@ static void check_entropy_operands(const char* op, const std::shared_ptr<JpegHuf
   TORCH_CHECK(status.numel() >= pk->n && pk->n < (1ll << 31), op, ": status buffer too small");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(bytes.data_ptr()) % 16 == 0, op, ": bytes must be 16-byte aligned");
   TORCH_CHECK(pk->desc.numel() == pk->n * (int64_t)sizeof(JpegHuffDesc) &&
-                  pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet), op, ": packed batch changed");
+                  pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet) &&
+                  pk->scans.numel() == pk->nscans * (int64_t)sizeof(JpegProgScan) &&
+                  pk->tabs.numel() == pk->ntabs * (int64_t)sizeof(JpegHuffTab) && pk->prog_list.numel() == pk->n_prog &&
+                  pk->ntabs < (1ll << 31), op, ": packed batch changed");
+}
+
+// The progressive entries of a packed batch (gpu == 3), one lane each, into the same coefs / status on
+// the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with allow_prog.
+static void launch_progressive(const char* op, const std::shared_ptr<JpegHuffPacked>& pk, const torch::Tensor& bytes,
+                               const torch::Tensor& dev_desc, torch::Tensor& coefs, torch::Tensor& status) {
+  if (pk->n_prog == 0) return;
+  const char* why = jpeg_huff_prog_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
+                                         reinterpret_cast<const JpegProgScan*>(pk->scans.data_ptr()), pk->nscans,
+                                         pk->ntabs);
+  TORCH_CHECK(why == nullptr, op, ": progressive descriptor outside its buffer: ", why ? why : "");
+  const int32_t* lp = pk->prog_list.data_ptr<int32_t>();
+  const auto* hd = reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr());
+  for (int64_t j = 0; j < pk->n_prog; ++j)
+    TORCH_CHECK(lp[j] >= 0 && lp[j] < pk->n && hd[lp[j]].gpu == 3, op, ": packed batch changed");
+  auto dev_scans = pk->scans.to(bytes.device());
+  auto dev_tabs = pk->tabs.to(bytes.device());
+  auto dev_list = pk->prog_list.to(bytes.device());
+  jpeg_entropy_prog_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffTab*>(dev_tabs.data_ptr()),
+                           (int)pk->ntabs, reinterpret_cast<const JpegProgScan*>(dev_scans.data_ptr()), pk->nscans,
+                           reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), (int)pk->n,
+                           dev_list.data_ptr<int32_t>(), (int)pk->n_prog, coefs.data_ptr<int16_t>(),
+                           status.data_ptr<int>(), cur_stream());
+  check_launch("jpeg_entropy_prog");
 }
 
 // Decodes the packed batch into coefs (zeroed by the caller: jpeg_entropy_zero) on the current
@@ -340,14 +393,17 @@ void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor b
   if (pk->n_gpu == 0) return;
   check_entropy_operands("jpeg_entropy_gpu", pk, bytes, coefs, status);
   const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
-                                    bytes.numel(), pk->nsets, coefs.numel());
+                                    bytes.numel(), pk->nsets, coefs.numel(), pk->native_progressive);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
-  jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr()),
-                      reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), coefs.data_ptr<int16_t>(),
-                      status.data_ptr<int>(), (int)pk->n, cur_stream());
-  check_launch("jpeg_entropy");
+  if (pk->n_lane) {
+    jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr()),
+                        reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), coefs.data_ptr<int16_t>(),
+                        status.data_ptr<int>(), (int)pk->n, cur_stream());
+    check_launch("jpeg_entropy");
+  }
+  launch_progressive("jpeg_entropy_gpu", pk, bytes, dev_desc, coefs, status);
 }
 
 // The same for a batch packed with parallel = true: the sub-stream kernel on the entries laid out
@@ -363,7 +419,8 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
   TORCH_CHECK(pk->par.numel() == pk->n * (int64_t)sizeof(JpegParDesc), "jpeg_entropy_gpu_parallel: packed batch changed");
   const char* why = jpeg_huff_par_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()),
                                         reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n,
-                                        bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits);
+                                        bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits,
+                                        pk->native_progressive);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu_parallel: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
@@ -381,6 +438,7 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
                             reinterpret_cast<uint32_t*>(scratch.data_ptr<int>()), (int)pk->n, cur_stream());
     check_launch("jpeg_entropy_par");
   }
+  launch_progressive("jpeg_entropy_gpu_parallel", pk, bytes, dev_desc, coefs, status);
 }
 
 // Measurement helper (tools/jpeg_bench.py): the synchronisation rounds the sub-stream kernel needs for
@@ -437,10 +495,12 @@ void jpeg_entropy_zero(torch::Tensor coefs) {
 
 // JpegPlan and JpegHuffPacked are complete types only here, so this family registers itself.
 void bind_jpeg(py::module_& m) {
-  m.def("jpeg_parse", &jpeg_parse, "JPEG markers up to SOS: (status, reason, header dict or None)");
+  m.def("jpeg_parse", &jpeg_parse, "JPEG markers up to SOS (native_progressive: of a progressive file up to EOI): "
+        "(status, reason, header dict or None)", py::arg("data"), py::arg("native_progressive") = false);
   m.def("jpeg_entropy_batch", &jpeg_entropy_batch,
         "baseline JPEG entropy decode of a list of bytes / None on native threads (GIL released): "
-        "(status, headers, int16 coefficients on the host, offsets)", py::arg("datas"), py::arg("threads") = 8);
+        "(status, headers, int16 coefficients on the host, offsets)", py::arg("datas"), py::arg("threads") = 8,
+        py::arg("native_progressive") = false);
   py::class_<JpegPlan, std::shared_ptr<JpegPlan>>(m, "JpegPlan")
       .def_readonly("n_gpu", &JpegPlan::n_gpu)
       .def_readonly("nblocks", &JpegPlan::nblocks)
@@ -466,11 +526,17 @@ void bind_jpeg(py::module_& m) {
       .def_readonly("parallel", &JpegHuffPacked::parallel)
       .def_readonly("n_par", &JpegHuffPacked::n_par)
       .def_readonly("n_lane", &JpegHuffPacked::n_lane)
-      .def_readonly("scratch_total", &JpegHuffPacked::scratch_total);
+      .def_readonly("scratch_total", &JpegHuffPacked::scratch_total)
+      .def_readonly("native_progressive", &JpegHuffPacked::native_progressive)
+      .def_readonly("n_prog", &JpegHuffPacked::n_prog)
+      .def_readonly("nscans", &JpegHuffPacked::nscans)
+      .def_readonly("ntabs", &JpegHuffPacked::ntabs);
   m.def("jpeg_huff_pack", &jpeg_huff_pack,
         "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage "
         "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel)",
-        py::arg("datas"), py::arg("parallel") = false);
+        py::arg("datas"), py::arg("parallel") = false, py::arg("native_progressive") = false);
+  m.attr("JPEG_PROG_MAX_SCANS") = (int64_t)kJpegProgMaxScans;
+  m.attr("JPEG_HEADER_PROGRESSIVE_OFFSET") = (int64_t)offsetof(JpegHeader, progressive);   // an int, in the header rows
   m.attr("JPEG_PAR_SUB_BITS") = (int64_t)kJpegParSubBits;
   m.attr("JPEG_PAR_THREADS") = (int64_t)kJpegParThreads;
   m.attr("JPEG_PAR_MAX_ROUNDS") = (int64_t)kJpegParMaxRounds;

@@ -58,6 +58,10 @@ struct JpegHuffDesc {
   int32_t ncomp, mcux, mcuy, restart_interval;
   int32_t h[3], v[3], bw[3], bh[3], td[3], ta[3];
   uint32_t coef_off[3];
+  // gpu == 3 only (a progressive file, jpeg_huff_prog.h): each component's own block grid and
+  // the image's range in the batch's JpegProgScan array; set_idx, td, ta, restart_interval unused
+  int32_t gw[3], gh[3];
+  int32_t scan_first, nscans;
 };
 
 namespace jpeg_huff_detail {

@@ -292,5 +292,13 @@ struct JpegParDesc;
 void jpeg_entropy_par_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
                              const JpegParDesc* par, int16_t* coef, int* status, uint32_t* scratch, int n,
                              hipStream_t st);
+// one lane per entry of list[0, nlist), the batch's progressive entries (gpu == 3 in desc[0, n)): every
+// scan of the image with the core of jpeg_huff_prog.h; status[list[j]] is written.  The caller has run
+// jpeg_huff_check(..., allow_prog) and jpeg_huff_prog_check over desc, scans and the table count.
+struct JpegHuffTab;
+struct JpegProgScan;
+void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int ntabs, const JpegProgScan* scans,
+                              long long nscans, const JpegHuffDesc* desc, int n, const int* list, int nlist,
+                              int16_t* coef, int* status, hipStream_t st);
 
 }  // namespace idunno

@@ -14,15 +14,19 @@
 // int16 writes into a buffer the launcher zeroed.
 //
 // jpeg_entropy_par_kernel (entropy_on="gpu_parallel", further down) decodes one
-// image on a whole workgroup instead.
+// image on a whole workgroup instead.  jpeg_entropy_prog_kernel
+// (progressive="native", last) decodes the progressive files of a batch, one lane
+// per image like the first, in either device form.
 //
 // The host (bind_jpeg.cpp jpeg_entropy_gpu / jpeg_entropy_gpu_parallel) has checked every descriptor against
-// the three buffers with jpeg_huff_check before the launch; inside a span the
+// the three buffers with jpeg_huff_check before the launch (the progressive entries'
+// scan ranges and table indices with jpeg_huff_prog_check); inside a span the
 // core checks every access itself.
 #include <hip/hip_runtime.h>
 
 #include "../jpeg_huff_core.h"
 #include "../jpeg_huff_par.h"
+#include "../jpeg_huff_prog.h"
 #include "../kernels.h"
 
 namespace idunno {
@@ -124,7 +128,40 @@ __global__ __launch_bounds__(kJpegParThreads) void jpeg_entropy_par_kernel(
   if (t == 0) status[i] = bad ? kJpegHuffCorrupt : kJpegHuffOk;
 }
 
+// Progressive files (progressive="native", gpu == 3): one lane decodes every scan of
+// one image with the core of jpeg_huff_prog.h, in workgroups of one wave like
+// jpeg_entropy_kernel.  The grid runs over `list`, the compact indices of the
+// batch's progressive entries, so a batch with a few progressive files among many
+// baseline ones does not launch waves of idle lanes.  A refinement scan reads back
+// the coefficients the same lane stored in an earlier scan of the same launch:
+// plain loads and stores of one thread to its own span, in program order.  Tables
+// are single JpegHuffTabs (1.5 KB) in global memory, shared by the images that
+// carry identical ones.
+__global__ __launch_bounds__(64) void jpeg_entropy_prog_kernel(const uint8_t* __restrict__ bytes,
+                                                               const JpegHuffTab* __restrict__ tabs, int ntabs,
+                                                               const JpegProgScan* __restrict__ scans, long long nscans,
+                                                               const JpegHuffDesc* __restrict__ desc, int n,
+                                                               const int* __restrict__ list, int nlist,
+                                                               int16_t* coef, int* __restrict__ status) {
+  const int j = (int)(blockIdx.x * 64u + threadIdx.x);
+  if (j >= nlist) return;
+  const int i = list[j];
+  if (i < 0 || i >= n) return;
+  const JpegHuffDesc& d = desc[i];
+  if (d.gpu != 3) return;
+  status[i] = jpeg_prog_decode_image(d, scans, nscans, reinterpret_cast<const uint32_t*>(bytes + d.byte_off), tabs,
+                                     ntabs, coef + d.coef_base);
+}
+
 }  // namespace
+
+void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int ntabs, const JpegProgScan* scans,
+                              long long nscans, const JpegHuffDesc* desc, int n, const int* list, int nlist,
+                              int16_t* coef, int* status, hipStream_t st) {
+  if (nlist <= 0) return;
+  hipLaunchKernelGGL(jpeg_entropy_prog_kernel, dim3((unsigned)((nlist + 63) / 64)), dim3(64), 0, st, bytes, tabs, ntabs,
+                     scans, nscans, desc, n, list, nlist, coef, status);
+}
 
 void jpeg_entropy_par_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
                              const JpegParDesc* par, int16_t* coef, int* status, uint32_t* scratch, int n,

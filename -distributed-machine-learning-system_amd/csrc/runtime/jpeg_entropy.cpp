@@ -4,6 +4,10 @@
 // and every write of a coefficient through an index check (k <= 63 inside a
 // block that the header-derived layout places inside the output span), so
 // arbitrary bytes give a status, never an out-of-range access.
+//
+// With native_progressive the parser also walks a progressive file's scans up
+// to EOI into a scan script, and jpeg_decode runs the shared scan core of
+// ../jpeg_huff_prog.h over it; baseline files take the same path as without it.
 #include "jpeg_entropy.h"
 
 #include <algorithm>
@@ -78,12 +82,59 @@ struct Scan {
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
-int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) {
+// The DHT payloads of a progressive file's table slots (dc 0..3, ac 0..3), kept
+// because each SOS of the scan script latches the tables in effect there.
+struct RawTabs {
+  std::string key[8];     // class byte, 16 counts, the symbols; empty: undefined
+};
+
+// the table of a DHT payload build_huff has accepted, in the core's form
+void build_core_tab(const std::string& key, JpegHuffTab* t) {
+  const uint8_t* counts = reinterpret_cast<const uint8_t*>(key.data()) + 1;
+  const uint8_t* vals = counts + 16;
+  std::memset(t, 0, sizeof(*t));
+  t->maxcode[0] = -1;
+  t->nvals = (int32_t)key.size() - 17;
+  std::memcpy(t->vals, vals, (size_t)t->nvals);
+  int32_t code = 0;
+  int k = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int cnt = counts[l - 1];
+    t->valptr[l] = k;
+    t->mincode[l] = code;
+    t->maxcode[l] = cnt ? code + cnt - 1 : -1;
+    if (l <= kJpegHuffLookBits) {
+      const int rep = 1 << (kJpegHuffLookBits - l);
+      for (int i = 0; i < cnt; ++i)
+        for (int j = 0; j < rep; ++j) t->look[(code + i) * rep + j] = (uint16_t)((l << 8) | vals[k + i]);
+    }
+    k += cnt;
+    code = (code + cnt) << 1;
+  }
+}
+
+// index of the slot's table in script->tabs, added on first use
+int script_tab(const RawTabs& raw, int slot, JpegProgScript* script) {
+  const std::string& key = raw.key[slot];
+  for (size_t i = 0; i < script->tab_keys.size(); ++i)
+    if (script->tab_keys[i] == key) return (int)i;
+  script->tab_keys.push_back(key);
+  script->tabs.emplace_back();
+  build_core_tab(key, &script->tabs.back());
+  return (int)script->tabs.size() - 1;
+}
+
+// native: an SOF2 frame is walked to EOI (script, when given, receives its scans)
+int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, bool native = false,
+          JpegProgScript* script = nullptr) {
   if (data == nullptr || n == 0) return JPEG_EMPTY;
   if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_NOT_JPEG;
   std::memset(hdr, 0, sizeof(*hdr));
+  if (script != nullptr) *script = JpegProgScript{};
   bool have_sof = false;
   int comp_id[3] = {0, 0, 0};
+  bool latched[3] = {false, false, false};
+  std::vector<RawTabs> rawv(native ? 1 : 0);            // off the stack
   size_t pos = 2;
   for (;;) {
     if (pos + 2 > n || data[pos] != 0xFF) return JPEG_CORRUPT;
@@ -91,6 +142,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
     if (pos >= n) return JPEG_CORRUPT;
     const int m = data[pos++];
     if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;   // stand-alone markers
+    if (m == 0xD9 && hdr->progressive && hdr->nscans > 0) return JPEG_OK;   // the walk's end
     if (m == 0xD8 || m == 0xD9 || m == 0x00) return JPEG_CORRUPT;
     if (pos + 2 > n) return JPEG_CORRUPT;
     const int L = be16(data + pos);
@@ -99,12 +151,13 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
     const size_t slen = (size_t)L - 2;
     pos += (size_t)L;
     switch (m) {
-      case 0xC2:
-        return JPEG_UNSUPPORTED_PROGRESSIVE;
       case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC8:
         return JPEG_UNSUPPORTED_SOF;
       case 0xC9: case 0xCA: case 0xCB: case 0xCC: case 0xCD: case 0xCE: case 0xCF:
         return JPEG_UNSUPPORTED_ARITHMETIC;
+      case 0xC2:
+        if (!native) return JPEG_UNSUPPORTED_PROGRESSIVE;
+        [[fallthrough]];                                 // the same frame header
       case 0xC0: case 0xC1: {
         if (have_sof || slen < 6) return JPEG_CORRUPT;
         if (seg[0] != 8) return JPEG_UNSUPPORTED_PRECISION;
@@ -145,6 +198,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
           off += (uint32_t)cp.bw * (uint32_t)cp.bh * 64u;
         }
         hdr->total_coefs = off;
+        hdr->progressive = m == 0xC2;
         have_sof = true;
         break;
       }
@@ -167,6 +221,11 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
           if (tc > 1 || th > 3) return JPEG_CORRUPT;
           const int used = build_huff(seg + p + 1, slen - p - 1, tc ? &tb->ac[th] : &tb->dc[th]);
           if (used < 0) return JPEG_CORRUPT;
+          if (native) {
+            std::string& key = rawv[0].key[4 * tc + th];
+            key.assign(reinterpret_cast<const char*>(seg + p), 1 + (size_t)used);
+            key[0] = (char)tc;                           // the slot does not tell tables apart
+          }
           p += 1 + (size_t)used;
         }
         break;
@@ -179,6 +238,57 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
         if (!have_sof || slen < 1) return JPEG_CORRUPT;
         const int ns = seg[0];
         if (ns < 1 || ns > 4 || slen != (size_t)(4 + 2 * ns)) return JPEG_CORRUPT;
+        if (hdr->progressive) {
+          if (hdr->nscans >= kJpegProgMaxScans) return JPEG_UNSUPPORTED_MULTISCAN;
+          if (ns > hdr->ncomp) return JPEG_CORRUPT;
+          const RawTabs& raw = rawv[0];
+          JpegProgScan s;
+          std::memset(&s, 0, sizeof(s));
+          s.ncomp = ns;
+          s.ac_tab = s.dc_tab[0] = s.dc_tab[1] = s.dc_tab[2] = -1;
+          const uint8_t* t = seg + 1 + 2 * ns;
+          s.ss = t[0];
+          s.se = t[1];
+          s.ah = t[2] >> 4;
+          s.al = t[2] & 15;
+          if (s.se > 63 || s.ss > s.se || s.al > 13 || (s.ah != 0 && s.ah != s.al + 1)) return JPEG_CORRUPT;
+          if (s.ss == 0 ? s.se != 0 : ns != 1) return JPEG_CORRUPT;
+          int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+          for (int c = 0; c < ns; ++c) {
+            int ci = -1;
+            for (int f = 0; f < hdr->ncomp; ++f)
+              if (comp_id[f] == seg[1 + 2 * c]) ci = f;
+            if (ci < 0 || (c > 0 && ci <= s.comp[c - 1])) return JPEG_CORRUPT;   // frame order, none twice
+            s.comp[c] = ci;
+            td[c] = seg[2 + 2 * c] >> 4;
+            ta[c] = seg[2 + 2 * c] & 15;
+            if (td[c] > 3 || ta[c] > 3) return JPEG_CORRUPT;
+            // only the table the scan decodes with has to exist: DC first scans a DC table, AC scans an AC table
+            if (s.ss == 0 ? (s.ah == 0 && raw.key[td[c]].empty()) : raw.key[4 + ta[c]].empty()) return JPEG_CORRUPT;
+            if (!latched[ci]) {
+              if (!tb->qdef[hdr->comp[ci].qidx]) return JPEG_CORRUPT;
+              std::memcpy(hdr->comp[ci].q, tb->q[hdr->comp[ci].qidx], sizeof(hdr->comp[ci].q));
+              latched[ci] = true;
+            }
+          }
+          if (hdr->nscans == 0) hdr->scan_pos = (uint32_t)pos;
+          if (script != nullptr) {
+            if (hdr->nscans == 0) script->first_pos = (uint32_t)pos;
+            s.byte_off = (uint32_t)(pos - script->first_pos);
+            s.restart_interval = hdr->restart_interval;
+            for (int c = 0; c < ns; ++c)
+              if (s.ss == 0 && s.ah == 0) s.dc_tab[c] = script_tab(raw, td[c], script);
+            if (s.ss != 0) s.ac_tab = script_tab(raw, 4 + ta[0], script);
+            script->scans.push_back(s);
+          }
+          ++hdr->nscans;
+          // over the entropy-coded data to the next marker that is not RSTn; none: no EOI
+          while (pos + 1 < n && !(data[pos] == 0xFF && data[pos + 1] != 0x00 && data[pos + 1] != 0xFF &&
+                                  !(data[pos + 1] >= 0xD0 && data[pos + 1] <= 0xD7)))
+            ++pos;
+          if (pos + 1 >= n) return JPEG_CORRUPT;
+          break;
+        }
         if (ns != hdr->ncomp) return JPEG_UNSUPPORTED_MULTISCAN;
         for (int c = 0; c < ns; ++c) {
           if (seg[1 + 2 * c] != comp_id[c]) return JPEG_CORRUPT;
@@ -193,6 +303,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc) 
         const uint8_t* t = seg + 1 + 2 * ns;
         if (t[0] != 0 || t[1] != 63 || t[2] != 0) return JPEG_CORRUPT;
         hdr->scan_pos = (uint32_t)pos;
+        hdr->nscans = 1;
         return JPEG_OK;
       }
       default:                                           // APPn, COM and anything else with a length
@@ -330,20 +441,61 @@ const char* jpeg_status_name(int status) {
   return status >= 0 && status < JPEG_STATUS_COUNT ? names[status] : "unknown";
 }
 
-int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr) {
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive, JpegProgScript* script) {
   std::vector<Tables> tb(1);                             // ~9 KB: off the stack
   Scan sc;
-  return parse(data, n, hdr, &tb[0], &sc);
+  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script);
 }
 
-int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap) {
+void jpeg_prog_frame_desc(const JpegHeader& h, JpegHuffDesc* d) {
+  d->total_coefs = h.total_coefs;
+  d->ncomp = h.ncomp;
+  d->mcux = h.mcux;
+  d->mcuy = h.mcuy;
+  for (int c = 0; c < h.ncomp && c < 3; ++c) {
+    const JpegComp& cp = h.comp[c];
+    d->h[c] = cp.h;
+    d->v[c] = cp.v;
+    d->bw[c] = cp.bw;
+    d->bh[c] = cp.bh;
+    d->coef_off[c] = cp.coef_off;
+    d->gw[c] = ((h.W * cp.h + h.hmax - 1) / h.hmax + 7) / 8;
+    d->gh[c] = ((h.H * cp.v + h.vmax - 1) / h.vmax + 7) / 8;
+  }
+}
+
+namespace {
+
+// a progressive file parse() accepted, with the shared core: the scans' bytes (first scan's
+// data to the end of the file) go to a word-aligned, padded copy, which is what Bits reads
+int decode_progressive(const uint8_t* data, size_t n, const JpegHeader& hdr, const JpegProgScript& script,
+                       int16_t* out) {
+  if (script.first_pos > n || n - script.first_pos > 0xFFFFFFF0u) return JPEG_CORRUPT;
+  JpegHuffDesc d;
+  std::memset(&d, 0, sizeof(d));
+  jpeg_prog_frame_desc(hdr, &d);
+  d.byte_len = (uint32_t)(n - script.first_pos);
+  d.byte_span = (d.byte_len + (uint32_t)kJpegHuffBytePad - 1u) / (uint32_t)kJpegHuffBytePad * (uint32_t)kJpegHuffBytePad;
+  d.scan_first = 0;
+  d.nscans = (int32_t)script.scans.size();
+  std::vector<uint32_t> words(d.byte_span / 4 + 1, 0u);
+  std::memcpy(words.data(), data + script.first_pos, d.byte_len);
+  return jpeg_prog_decode_image(d, script.scans.data(), (long long)script.scans.size(), words.data(),
+                                script.tabs.data(), (int32_t)script.tabs.size(), out);
+}
+
+}  // namespace
+
+int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, bool native_progressive) {
   std::vector<Tables> tbv(1);
   Tables& tb = tbv[0];
   Scan sc;
-  const int st = parse(data, n, hdr, &tb, &sc);
+  JpegProgScript script;
+  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr);
   if (st != JPEG_OK) return st;
   if (out == nullptr || (size_t)hdr->total_coefs > out_cap) return JPEG_BUFFER_TOO_SMALL;
   std::memset(out, 0, (size_t)hdr->total_coefs * sizeof(int16_t));
+  if (hdr->progressive) return decode_progressive(data, n, *hdr, script, out);
   BitReader br;
   br.data = data;
   br.p = hdr->scan_pos;
@@ -377,13 +529,14 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
 }
 
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
-                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads) {
+                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads,
+                       bool native_progressive) {
   std::atomic<int> next{0};
   auto work = [&]() {
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) return;
-      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i]);
+      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive);
     }
   };
   const int nt = std::max(1, std::min(nthreads, n));

@@ -8,9 +8,16 @@
 // (row-major u + 8 v) order, 64 per block, blocks row-major over the component's
 // padded block grid (bw x bh = MCU grid x sampling factors); components follow
 // each other at JpegComp::coef_off (in int16 elements).
+//
+// Progressive files (SOF2) are refused unless a caller passes native_progressive;
+// then they decode into the same layout (../jpeg_huff_prog.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../jpeg_huff_prog.h"
 
 namespace idunno {
 
@@ -26,7 +33,7 @@ enum JpegStatus : int {
   JPEG_UNSUPPORTED_QUANT16 = 8,     // 16-bit quantisation tables
   JPEG_UNSUPPORTED_SAMPLING = 9,    // not 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2)
   JPEG_UNSUPPORTED_SIZE = 10,       // above 4096 x 4096
-  JPEG_UNSUPPORTED_MULTISCAN = 11,  // baseline with one scan per component
+  JPEG_UNSUPPORTED_MULTISCAN = 11,  // baseline with one scan per component; progressive above kJpegProgMaxScans
   JPEG_UNSUPPORTED_SOF = 12,        // lossless / hierarchical frames
   JPEG_BUFFER_TOO_SMALL = 13,       // caller's coefficient buffer < JpegHeader::total_coefs
   JPEG_STATUS_COUNT = 14,
@@ -54,19 +61,49 @@ struct JpegHeader {
   uint32_t total_coefs;   // int16 elements the coefficient buffer must hold
   uint32_t scan_pos;      // byte offset of the entropy-coded data
   JpegComp comp[3];
+  int progressive;        // 1: an SOF2 frame, accepted because the caller asked for native progressive decoding
+  int nscans;             // its scans (1 for a baseline file)
+};
+
+// The scan script of a progressive file, in the form jpeg_huff_prog.h decodes: what
+// the marker walk over the whole file (every SOS up to EOI) found.
+struct JpegProgScript {
+  std::vector<JpegProgScan> scans;     // byte_off relative to first_pos; table indices into tabs
+  std::vector<JpegHuffTab> tabs;       // the tables in effect at some SOS, identical ones once
+  std::vector<std::string> tab_keys;   // their DHT payloads (class, counts, symbols): what "identical" means
+  uint32_t first_pos = 0;              // byte offset of the first scan's entropy-coded data in the file
 };
 
 // Parses the markers up to and including SOS.  Fills *hdr on JPEG_OK.
-int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr);
+// native_progressive: an SOF2 frame of a supported layout is not refused with
+// JPEG_UNSUPPORTED_PROGRESSIVE; the walk then goes on over every scan up to EOI
+// (hdr->progressive, hdr->nscans; *script, when given, receives the scan script).
+// It refuses as JPEG_CORRUPT a scan with Ss == 0 and Se != 0, an AC scan of more
+// than one component, Se > 63, Ss > Se, Al > 13, a refinement with Ah != Al + 1,
+// a scan that uses an undefined table and a file without EOI; more than
+// kJpegProgMaxScans scans are JPEG_UNSUPPORTED_MULTISCAN.  A component's
+// quantisation table is the one in its slot at that component's first scan.
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive = false,
+                      JpegProgScript* script = nullptr);
+
+// The frame layout of *hdr in a JpegHuffDesc (ncomp, MCU grid, per component
+// sampling, padded grid, own grid, coefficient offsets, total_coefs): what
+// jpeg_prog_decode_scan reads besides the byte span.
+void jpeg_prog_frame_desc(const JpegHeader& hdr, JpegHuffDesc* d);
 
 // Parses and decodes one image into out[0, out_cap) (int16 elements).  Never
 // reads outside data[0, n) nor writes outside out[0, out_cap).
-int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap);
+// native_progressive: a progressive file is decoded with the core of
+// jpeg_huff_prog.h on a word-aligned copy of its scans; baseline files are
+// decoded as without it.
+int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap,
+                bool native_progressive = false);
 
 // Decodes n images on a pool of `nthreads` std::threads (never derived from
 // the machine's CPU count).  Image i with data[i] == nullptr is skipped with
 // JPEG_EMPTY.  status[i] and hdr[i] are written for every i.
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
-                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads = 8);
+                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads = 8,
+                       bool native_progressive = false);
 
 }  // namespace idunno

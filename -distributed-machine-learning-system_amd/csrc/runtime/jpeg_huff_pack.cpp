@@ -141,9 +141,13 @@ size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 }  // namespace
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits) {
+                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
+  out->scans.clear();
+  out->tabs.clear();
+  std::map<std::string, int> seen_tabs;
+  JpegProgScript script;
   out->byte_total = out->coef_total = out->scratch_total = 0;
   out->par.clear();
   if (par_sub_bits) out->par.assign((size_t)n, JpegParDesc{});
@@ -156,9 +160,44 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       status[i] = JPEG_EMPTY;
       continue;
     }
-    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i]);
+    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script);
     if (status[i] != JPEG_OK) continue;
     const JpegHeader& h = hdr[i];
+    if (h.progressive) {
+      // the whole file from the first scan's data on, stuffed as it is; one descriptor per scan,
+      // its tables one JpegHuffTab at a time, identical ones shared across the batch
+      if (script.first_pos > len[i] || len[i] - script.first_pos > 0xFFFFFFF0u || script.scans.empty() ||
+          out->scans.size() + script.scans.size() > 0x7FFFFFFFu) {
+        status[i] = JPEG_CORRUPT;
+        continue;
+      }
+      std::vector<int> remap(script.tabs.size());
+      for (size_t t = 0; t < script.tabs.size(); ++t) {
+        auto it = seen_tabs.find(script.tab_keys[t]);
+        if (it == seen_tabs.end()) {
+          it = seen_tabs.emplace(script.tab_keys[t], (int)out->tabs.size()).first;
+          out->tabs.push_back(script.tabs[t]);
+        }
+        remap[t] = it->second;
+      }
+      d.gpu = 3;
+      d.scan_first = (int32_t)out->scans.size();
+      d.nscans = (int32_t)script.scans.size();
+      for (JpegProgScan s : script.scans) {
+        for (int c = 0; c < 3; ++c)
+          if (s.dc_tab[c] >= 0) s.dc_tab[c] = remap[(size_t)s.dc_tab[c]];
+        if (s.ac_tab >= 0) s.ac_tab = remap[(size_t)s.ac_tab];
+        out->scans.push_back(s);
+      }
+      jpeg_prog_frame_desc(h, &d);
+      d.byte_off = out->byte_total;
+      d.byte_len = (uint32_t)(len[i] - script.first_pos);
+      d.byte_span = (uint32_t)round_up(d.byte_len, kJpegHuffBytePad);
+      out->byte_total = round_up(d.byte_off + d.byte_span, kJpegHuffByteAlign);
+      d.coef_base = out->coef_total;
+      out->coef_total += (int64_t)h.total_coefs;
+      continue;
+    }
     RawSet& rs = rsv[0];
     rs = RawSet{};
     if (h.scan_pos > len[i] || len[i] - h.scan_pos > 0xFFFFFFF0u || !read_tables(data[i], len[i], h, &rs)) {
@@ -241,19 +280,19 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 namespace {
 
 const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
-                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits) {
+                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
   int64_t scratch_at = 0;
   if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
   for (int i = 0; i < n; ++i) {
     const JpegHuffDesc& d = desc[i];
     if (!d.gpu) continue;
-    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr)) return "gpu flag";
+    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr) && !(d.gpu == 3 && allow_prog)) return "gpu flag";
     if (d.byte_off < byte_at || d.byte_off % kJpegHuffByteAlign != 0 || d.byte_len > d.byte_span ||
         d.byte_span % kJpegHuffBytePad != 0 || d.byte_off + (int64_t)d.byte_span > byte_cap)
       return "byte span outside the byte buffer";
     byte_at = d.byte_off + (int64_t)d.byte_span;
-    if (d.set_idx < 0 || d.set_idx >= nsets) return "table set index";
+    if (d.gpu != 3 && (d.set_idx < 0 || d.set_idx >= nsets)) return "table set index";
     if (d.coef_base < coef_at || d.coef_base % 64 != 0 || d.coef_base + (int64_t)d.total_coefs > coef_cap)
       return "coefficient span outside the coefficient buffer";
     coef_at = d.coef_base + (int64_t)d.total_coefs;
@@ -286,14 +325,50 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
 
 }  // namespace
 
-const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap) {
-  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0);
+const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
+                            bool allow_prog) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog);
 }
 
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
-                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits) {
+                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
+                                bool allow_prog) {
   if (par == nullptr) return "no sub-stream descriptors";
-  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits);
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog);
+}
+
+const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
+                                 int64_t ntabs) {
+  int64_t scan_at = 0;                    // ranges ascend with the entries
+  for (int i = 0; i < n; ++i) {
+    const JpegHuffDesc& d = desc[i];
+    if (d.gpu != 3) continue;
+    if (scans == nullptr || d.nscans < 1 || d.nscans > kJpegProgMaxScans || (int64_t)d.scan_first < scan_at ||
+        (int64_t)d.scan_first + d.nscans > nscans)
+      return "scan range outside the scan buffer";
+    scan_at = (int64_t)d.scan_first + d.nscans;
+    if (d.ncomp != 1 && d.ncomp != 3) return "frame";
+    for (int c = 0; c < d.ncomp; ++c)
+      if (d.gw[c] < 1 || d.gh[c] < 1 || d.gw[c] > d.bw[c] || d.gh[c] > d.bh[c] || d.gw[c] <= d.bw[c] - d.h[c] ||
+          d.gh[c] <= d.bh[c] - d.v[c])
+        return "component grid";
+    uint32_t off_at = 0;                  // scans follow each other in the span
+    for (int k = 0; k < d.nscans; ++k) {
+      const JpegProgScan& s = scans[d.scan_first + k];
+      if (s.byte_off < off_at || s.byte_off > d.byte_len) return "scan offset outside the byte span";
+      off_at = s.byte_off;
+      if (s.ncomp < 1 || s.ncomp > d.ncomp) return "scan components";
+      for (int q = 0; q < s.ncomp; ++q)
+        if (s.comp[q] < 0 || s.comp[q] >= d.ncomp || (q > 0 && s.comp[q] <= s.comp[q - 1])) return "scan components";
+      if (s.ss < 0 || s.se > 63 || s.ss > s.se || s.al < 0 || s.al > 13 || (s.ah != 0 && s.ah != s.al + 1) ||
+          (s.ss == 0 ? s.se != 0 : s.ncomp != 1) || s.restart_interval < 0 || s.restart_interval > 65535)
+        return "scan parameters";
+      for (int q = 0; q < s.ncomp; ++q)
+        if (s.ss == 0 && s.ah == 0 && (s.dc_tab[q] < 0 || s.dc_tab[q] >= ntabs)) return "DC table index";
+      if (s.ss != 0 && (s.ac_tab < 0 || s.ac_tab >= ntabs)) return "AC table index";
+    }
+  }
+  return nullptr;
 }
 
 }  // namespace idunno

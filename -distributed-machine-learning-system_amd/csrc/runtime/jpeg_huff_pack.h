@@ -25,6 +25,9 @@ struct JpegHuffBatch {
   // the sub-stream form (jpeg_huff_plan with par_sub_bits != 0), else empty / 0
   std::vector<JpegParDesc> par;     // one per entry, meaningful where desc[i].gpu == 2
   int64_t scratch_total = 0;        // uint32 elements of the batch scratch buffer
+  // progressive files (jpeg_huff_plan with native_progressive), else empty
+  std::vector<JpegProgScan> scans;  // the scan scripts of the gpu == 3 entries, back to back
+  std::vector<JpegHuffTab> tabs;    // the single tables those scans index; identical tables share one entry
 };
 
 // Parses every entry (data[i] == nullptr: JPEG_EMPTY) and lays the batch out.
@@ -35,8 +38,13 @@ struct JpegHuffBatch {
 // restart interval whose scan is shorter than kJpegParMaxBits gets gpu == 2, a byte
 // span sized for its de-stuffed words, a JpegParDesc and a scratch span; every
 // other accepted image keeps gpu == 1 and the stuffed layout of the one-lane kernel.
+// native_progressive: a progressive file of a supported layout is accepted too (else
+// JPEG_UNSUPPORTED_PROGRESSIVE) and gets gpu == 3 in either form: its byte span is
+// the file from the first scan's data to the end in the stuffed layout of gpu == 1,
+// and it names a range of out->scans (jpeg_huff_prog.h), whose tables are entries
+// of out->tabs.
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits = 0);
+                    JpegHuffBatch* out, uint32_t par_sub_bits = 0, bool native_progressive = false);
 
 // Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
 // zeroes the padding between them.  A gpu == 2 entry gets its de-stuffed words
@@ -48,12 +56,23 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 // table sets, coef_cap int16 elements): nullptr when every span lies inside them
 // and the layout inside each span is consistent, else what is wrong.  Run before
 // a launch.
-const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap);
+// allow_prog: gpu == 3 entries are taken (spans and frame; their scans: jpeg_huff_prog_check).
+const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
+                            bool allow_prog = false);
 
 // The same for a batch planned with par_sub_bits: gpu == 1 entries as above, gpu == 2
 // entries also against their JpegParDesc and the scratch buffer (scratch_cap uint32
 // elements, kJpegParStateWords per sub-stream of sub_bits bits).
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
-                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits);
+                                int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
+                                bool allow_prog = false);
+
+// The gpu == 3 entries against the scan buffer (nscans JpegProgScan) and the table
+// buffer (ntabs JpegHuffTab) the progressive kernel will get: every image's scan
+// range inside the scan buffer, every scan's offset inside the image's byte span,
+// its parameters within what the core accepts, every table index it will use inside
+// the table buffer.  Run next to jpeg_huff_check(..., allow_prog = true) before a launch.
+const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
+                                 int64_t ntabs);
 
 }  // namespace idunno

@@ -33,7 +33,7 @@ from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
-# (device, directory, entropy_on) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# (device, directory, entropy_on, progressive) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
 # index only; after replacing files of a directory call drop_gpu_sources()
 _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
@@ -57,7 +57,8 @@ def drop_gpu_sources() -> None:
 
 def deeplearning(filename: str, modelname: str, start_image: int, end_image: int, *,
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
-                 data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host"):
+                 data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host",
+                 progressive: str = "fallback"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
     ``decoder="gpu"`` decodes the JPEG files with the native entropy decoder and
@@ -66,11 +67,15 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     decodes with Pillow like ``"pil"``).  ``entropy_on="gpu"`` (with
     ``decoder="gpu"``) also decodes the Huffman streams on the device instead of
     on host threads, one lane per image, and ``"gpu_parallel"`` does so with one
-    workgroup per image; the default is ``"host"``."""
+    workgroup per image; the default is ``"host"``.  ``progressive="native"``
+    (with ``decoder="gpu"``) decodes progressive JPEG files natively in that
+    form instead of handing them to Pillow; the default is ``"fallback"``."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
     if entropy_on not in ("host", "gpu", "gpu_parallel"):
         raise ValueError(f"entropy_on must be 'host', 'gpu' or 'gpu_parallel', not {entropy_on!r}")
+    if progressive not in ("fallback", "native"):
+        raise ValueError(f"progressive must be 'fallback' or 'native', not {progressive!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -82,10 +87,10 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         src = SyntheticSource(data_seed, device)
     elif decoder == "gpu":
         with _LOCK:
-            key = (str(device), os.path.abspath(d), entropy_on)
+            key = (str(device), os.path.abspath(d), entropy_on, progressive)
             src = _GPU_SOURCES.get(key)
             if src is None:
-                src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on)
+                src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on, progressive=progressive)
     else:
         src = JpegSource(device, root=d)
     names = class_names()
@@ -112,9 +117,11 @@ def main(argv=None) -> int:
     ap.add_argument("--entropy", default="host", choices=["host", "gpu", "gpu_parallel"],
                     help="with --decoder gpu: Huffman decode on host threads, on the device (one lane per image), "
                          "or on the device with one workgroup per image")
+    ap.add_argument("--progressive", default="fallback", choices=["fallback", "native"],
+                    help="with --decoder gpu: progressive JPEG files through Pillow, or decoded natively")
     a = ap.parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
-                           decoder=a.decoder, entropy_on=a.entropy)
+                           decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

@@ -342,20 +342,24 @@ def synth_images(seed: int, start: int, n: int, device, hw: int = 224):
 
 # ---- JPEG decode (runtime/jpeg.py drives these) ---------------------------------------
 
-def jpeg_parse(data: bytes):
+def jpeg_parse(data: bytes, native_progressive: bool = False):
     """Markers of a JPEG up to SOS: (status, reason, header dict or None);
-    status 0 = a baseline file the native decoder takes."""
-    return load().jpeg_parse(data)
+    status 0 = a baseline file the native decoder takes.  With
+    ``native_progressive`` a progressive file is walked up to EOI and taken too."""
+    return load().jpeg_parse(data, bool(native_progressive))
 
 
-def jpeg_entropy_batch(datas, threads: int = 8):
+def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False):
     """Huffman-decode a list of ``bytes | None`` on ``threads`` native threads
     (GIL released): (status per entry, headers, int16 coefficients on the
     host, first coefficient of each entry or -1)."""
-    return load().jpeg_entropy_batch(datas, int(threads))
+    return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive))
 
 
-_JPEG_PAR_CONSTANTS = ("JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS")
+# the sub-stream kernel's constants, then the progressive decoder's: the scan cap of one file
+# (csrc/jpeg_huff_prog.h) and where a header row keeps its ``progressive`` int
+_JPEG_PAR_CONSTANTS = ("JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS", "JPEG_PROG_MAX_SCANS",
+                       "JPEG_HEADER_PROGRESSIVE_OFFSET")
 
 
 def __getattr__(name: str):
@@ -366,12 +370,15 @@ def __getattr__(name: str):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def jpeg_huff_pack(datas, parallel: bool = False):
+def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = False):
     """Parse a list of ``bytes | None`` and pack the accepted entries for the
     device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
     ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
-    ``bytes`` (host uint8 tensor, ``byte_total``), ``coef_total``, ``n_gpu``."""
-    return load().jpeg_huff_pack(datas, bool(parallel))
+    ``bytes`` (host uint8 tensor, ``byte_total``), ``coef_total``, ``n_gpu``.
+    ``native_progressive``: progressive files are packed too (``n_prog``
+    entries, one scan descriptor per scan) for the progressive kernel, which
+    ``jpeg_entropy_gpu`` / ``jpeg_entropy_gpu_parallel`` launch next to theirs."""
+    return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive))
 
 
 def jpeg_entropy_zero(coefs):

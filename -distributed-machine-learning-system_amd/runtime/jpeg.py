@@ -19,10 +19,20 @@ jpeg_entropy_par_kernel), so a small query no longer waits for one lane to walk
 a whole stream; files with restart markers keep the one-lane kernel in the same
 batch.
 
+``progressive="native"`` (opt-in, default ``"fallback"``) takes progressive
+files in all three forms.  One marker walk over the whole file
+(csrc/runtime/jpeg_entropy.cpp) turns its SOS segments into a scan script, and
+one core (csrc/jpeg_huff_prog.h: DC / AC, first / refinement, EOB runs, restart
+intervals) decodes it scan by scan into the same coefficient layout: on the
+host threads, or on the device with one lane per image (jpeg_entropy_prog_kernel,
+also under ``"gpu_parallel"``: there is no sub-stream form for progressive
+scans).  Everything after the entropy stage is unchanged.
+
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
 crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
-decoder does not take (progressive, arithmetic, 12-bit, CMYK, odd sampling,
+decoder does not take (progressive unless ``progressive="native"``,
+non-interleaved baseline, arithmetic, 12-bit, CMYK, odd sampling,
 corrupt, not a JPEG at all) are decoded by ``load_image_u8`` on the host and
 reported in ``info["fallbacks"]``; on a CPU device every image takes that
 path.  ``reference_backend`` is the float64 numpy model of the GPU chain.
@@ -46,22 +56,35 @@ def _C():
     return ops
 
 
-def parse(data: bytes):
-    """Header of a baseline JPEG the native decoder takes (dict: W, H, ncomp,
-    mode, comp[i] = h, v, bw, bh, coef_off, q), or the reason (str) it does not."""
-    st, reason, hdr = _C().jpeg_parse(bytes(data))
+PROGRESSIVE = ("fallback", "native")
+
+
+def _check_progressive(progressive: str) -> str:
+    if progressive not in PROGRESSIVE:
+        raise ValueError(f"progressive must be one of {PROGRESSIVE}, not {progressive!r}")
+    return progressive
+
+
+def parse(data: bytes, progressive: str = "fallback"):
+    """Header of a JPEG the native decoder takes (dict: W, H, ncomp, mode,
+    comp[i] = h, v, bw, bh, coef_off, q, progressive, nscans), or the reason
+    (str) it does not.  A progressive file is ``"progressive"`` unless
+    ``progressive="native"``."""
+    native = _check_progressive(progressive) == "native"
+    st, reason, hdr = _C().jpeg_parse(bytes(data), native)
     return hdr if st == 0 else reason
 
 
-def entropy_decode(data: bytes):
+def entropy_decode(data: bytes, progressive: str = "fallback"):
     """(header, int16 coefficients) of one image by the native host decoder, or
     the reason (str) it was refused."""
+    native = _check_progressive(progressive) == "native"
     data = bytes(data)
-    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1)
+    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native)
     if status[0] != 0:
-        st, reason, _ = _C().jpeg_parse(data)
+        st, reason, _ = _C().jpeg_parse(data, native)
         return reason if st != 0 else "corrupt"
-    return parse(data), coefs.numpy()
+    return parse(data, progressive), coefs.numpy()
 
 
 # ---- float64 model of the GPU chain ------------------------------------------------
@@ -193,9 +216,10 @@ _DEVICE_FORMS = ("gpu", "gpu_parallel")
 _UNSYNCED = 100           # kJpegHuffUnsynced: the sub-stream kernel's rounds hit their cap (device-only status)
 
 
-def _refusal(C, data: bytes, status: int) -> str:
-    """Why an entry is a fallback: the parse's reason, else what the entropy stage said."""
-    st, reason, _ = C.jpeg_parse(data)
+def _refusal(C, data: bytes, status: int, native: bool = False) -> str:
+    """Why an entry is a fallback: the parse's reason (in the progressive mode the batch
+    was decoded in), else what the entropy stage said."""
+    st, reason, _ = C.jpeg_parse(data, native)
     if st != 0:
         return reason
     return "unsynced" if status == _UNSYNCED else "corrupt"
@@ -207,21 +231,24 @@ def _check_entropy_on(entropy_on: str) -> str:
     return entropy_on
 
 
-def entropy_batch(datas, threads: int = 8, entropy_on: str = "host"):
+def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
     kernels).  With ``entropy_on="gpu"`` or ``"gpu_parallel"`` it only parses the
     headers and packs bytes, tables and descriptors for the entropy kernels (one
-    thread, GIL released as well).  Returns what ``decode_batch(..., entropy=)`` takes."""
+    thread, GIL released as well).  ``progressive="native"`` takes progressive
+    files in either form.  Returns what ``decode_batch(..., entropy=)`` takes;
+    the result remembers both options."""
     _check_entropy_on(entropy_on)
+    native = _check_progressive(progressive) == "native"
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
     if entropy_on in _DEVICE_FORMS:
-        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel")
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native)
         return entropy_on, datas, packed, time.perf_counter() - t0
-    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads))
-    return datas, status, hdr, coefs, offs, time.perf_counter() - t0
+    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native)
+    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive
 
 
 def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
@@ -255,24 +282,26 @@ def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
     return dev_coefs, dev_status, times
 
 
-def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8):
+def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8, progressive: str = "fallback"):
     """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
     from the host decoder or, with ``entropy_on="gpu"`` / ``"gpu_parallel"`` on a
-    GPU ``device``, from the entropy kernels."""
+    GPU ``device``, from the entropy kernels.  ``progressive="native"``:
+    progressive files are decoded too, in every form."""
     _check_entropy_on(entropy_on)
+    native = _check_progressive(progressive) == "native"
     C = _C()
     datas = [None if d is None else bytes(d) for d in datas]
     if entropy_on == "host":
-        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads))
+        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native)
         return list(status), list(offs), coefs
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel")
+    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native)
     status = list(packed.status)
     coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
     if packed.n_gpu:
@@ -288,7 +317,8 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
 
 
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
-                 stager: HbmStager | None = None, entropy=None, entropy_on: str = "host"):
+                 stager: HbmStager | None = None, entropy=None, entropy_on: str = "host",
+                 progressive: str = "fallback"):
     """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
     ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
     resized or cropped and the result is a list of [H, W, 3] tensors (``None``
@@ -313,8 +343,26 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     (sub-streams that synchronise themselves, csrc/jpeg_huff_par.h); files with
     restart markers take the one-lane kernel inside the same batch.  An image
     whose sub-streams did not synchronise within the kernel's round cap is an
-    ``"unsynced"`` fallback."""
+    ``"unsynced"`` fallback.
+
+    ``progressive="native"`` (default ``"fallback"``: a progressive file goes
+    to ``load_image_u8`` with the reason ``"progressive"``) decodes progressive
+    files of a supported layout (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 /
+    4:2:0, Huffman, at most ``JPEG_PROG_MAX_SCANS`` scans) natively in every
+    ``entropy_on`` form: on the host threads with the scan core of
+    csrc/jpeg_huff_prog.h, on the device with jpeg_entropy_prog_kernel, one
+    lane per image in both device forms (no sub-stream form for progressive
+    scans).  They hold the coefficients of their baseline twins, so the IDCT
+    and resize kernels see no difference.  A progressive file the decoder or
+    kernel refuses is then a ``"corrupt"`` fallback, one with more scans a
+    ``"multiscan"`` one.  ``info["progressive"]`` names the mode in effect
+    (when ``entropy`` was prepared, the one it was prepared in; on a CPU device
+    the one asked for, and nothing native runs), ``info["progressive_images"]``
+    counts the progressive files decoded natively.  Non-interleaved baseline
+    files (``"multiscan"``), arithmetic coding, 12-bit samples and CMYK remain
+    fallbacks."""
     _check_entropy_on(entropy_on)
+    _check_progressive(progressive)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
@@ -323,9 +371,12 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     if entropy is None:
         datas = [None if d is None else bytes(d) for d in datas]
     else:
+        # the form and the mode the entropy stage was prepared in decide
         datas = entropy[1] if on_gpu else entropy[0]
+        progressive = ("native" if entropy[2].native_progressive else "fallback") if on_gpu else entropy[6]
+    native = progressive == "native"
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
-            "gpu_images": 0, "entropy_on": form}
+            "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -344,10 +395,13 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         device = torch.device("cuda", torch.cuda.current_device())
     packed = None
     if on_gpu:
-        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form)
+        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form,
+                                                                                         progressive)
         status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
     else:
-        _, status, hdr, coefs, offs, info["entropy_s"] = entropy if entropy is not None else entropy_batch(datas, threads)
+        _, status, hdr, coefs, offs, info["entropy_s"] = (entropy if entropy is not None else
+                                                          entropy_batch(datas, threads, "host", progressive))[:6]
+        status = list(status)
         coef_elems = coefs.numel()
     geom = None
     if not full:
@@ -407,7 +461,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 imgs.append(None)
                 continue
             if status[i] != 0:
-                info["fallbacks"].append((i, _refusal(C, d, status[i])))
+                info["fallbacks"].append((i, _refusal(C, d, status[i], native)))
                 t = torch.from_numpy(host(d).copy()).to(device)
                 if full:
                     imgs.append(t)
@@ -417,6 +471,9 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 h, w = int(hdr[i].numpy().view(np.int32)[1]), int(hdr[i].numpy().view(np.int32)[0])
                 o = plan.out_off[i]
                 imgs.append(out[o:o + h * w * 3].view(h, w, 3))
+        if native and n:
+            prog = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_PROGRESSIVE_OFFSET // 4]
+            info["progressive_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and prog[i])
         # the result is complete when it is returned, whatever the batch held (the zero fill and
         # the fallbacks' copies too): a holder may hand it to a consumer on any other stream
         cur.synchronize()

@@ -25,7 +25,16 @@ form.  The synchronisation rounds the sub-stream kernel needs on these files are
 found on the host with the same code (``ops.jpeg_huff_par_rounds``).  Needs a
 GPU: without one it exits with an error.
 
+``--progressive`` measures the progressive files instead and nothing else: the
+same images encoded with ``progressive=True``, cold ``GpuJpegSource.get`` passes
+with ``progressive="fallback"`` (every file through Pillow in ``decode_batch``'s
+serial loop) against ``"native"``, for ``entropy_on="host"`` at ``--threads``,
+``"gpu"`` and ``"gpu_parallel"``: six arms alternating in one process, ``--reps``
+repetitions after a warm-up of every arm, then the cold query of each
+``--queries`` size for the same six arms.
+
     python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
+    python tools/jpeg_bench.py --progressive --queries 64 --out profiles/jpeg_bench_progressive.log
 """
 from __future__ import annotations
 
@@ -42,7 +51,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def make_images(d: str, n: int, seed: int = 0) -> int:
+def make_images(d: str, n: int, seed: int = 0, progressive: bool = False) -> int:
     """Smooth structure plus noise: files of a photograph's size (~40-60 KB), not of flat colour."""
     from PIL import Image
 
@@ -55,9 +64,84 @@ def make_images(d: str, n: int, seed: int = 0) -> int:
         a = np.stack([127.5 + 90 * np.sin(xx / fx[c] + ph[c]) * np.cos(yy / fy[c] + ph[3 + c]) for c in range(3)], 2)
         a = np.clip(a + rng.normal(0, 12, a.shape), 0, 255).astype(np.uint8)
         p = os.path.join(d, f"test_{i}.JPEG")
-        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2)
+        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2, progressive=progressive)
         total += os.path.getsize(p)
     return total
+
+
+def progressive_report(a, dev, say) -> None:
+    """``--progressive``: fallback against native on progressive files, six arms."""
+    import torch
+
+    from idunno.runtime.data import GpuJpegSource
+
+    n = a.images
+    arms = [(f"{on:12s} {mode}", on, mode) for on in ("host", "gpu", "gpu_parallel") for mode in ("fallback", "native")]
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        x = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, x
+
+    with tempfile.TemporaryDirectory() as d, torch.cuda.device(dev):
+        t0 = time.perf_counter()
+        nbytes = make_images(d, n, progressive=True)
+        say(f"{n} progressive images 500x375 4:2:0 q90, {nbytes / n / 1024:.1f} KiB each, generated in "
+            f"{time.perf_counter() - t0:.1f} s; {torch.cuda.get_device_name(0)}; {a.threads} threads (host form)")
+
+        def source(on, mode):
+            return GpuJpegSource(dev, root=d, threads=a.threads, entropy_on=on, progressive=mode)
+
+        def passes(q, label):
+            want = None
+            for _, on, mode in arms:                                # warm-up of every arm
+                src = source(on, mode)
+                got = src.get(0, q - 1)
+                assert src.fallbacks == (q if mode == "fallback" else 0), (on, mode, src.fallbacks)
+                assert src.progressive_images == (0 if mode == "fallback" else q)
+                if mode == "native":                                # the three native forms give the same pixels
+                    assert want is None or torch.equal(got, want), on
+                    want = got
+                else:
+                    diff = (got.int() - want.int()).abs() if want is not None else None
+                    if diff is not None:
+                        say(f"{label}: {on} fallback (Pillow) against native over {q} images: max |diff| "
+                            f"{int(diff.max())}, mean {float(diff.float().mean()):.4f}")
+                del got
+            del want
+            res = {name: {"s": [], "entropy_s": [], "cpu_s": []} for name, *_ in arms}
+            for r in range(a.reps):
+                for name, on, mode in arms:
+                    src = source(on, mode)
+                    c0 = time.process_time()
+                    dt, y = timed(lambda: src.get(0, q - 1))
+                    cpu = time.process_time() - c0
+                    assert src.decoded == q
+                    res[name]["s"].append(dt)
+                    res[name]["entropy_s"].append(src.seconds["entropy_s"])
+                    res[name]["cpu_s"].append(cpu)
+                    say(f"{label} rep {r}: {name:24s} {1e3 * dt:10.2f} ms  {q / dt:9.1f} img/s  entropy "
+                        f"{1e3 * src.seconds['entropy_s']:9.2f} ms  host CPU {cpu:7.3f} s")
+                    del y, src
+            return res
+
+        res = passes(n, "full pass")
+        say(f"progressive files, cold GpuJpegSource.get of {n} images (entropy: host wall over the decode threads / "
+            "device events of the kernels; fallback decodes in Pillow after them):")
+        for name, *_ in arms:
+            v = [n / s for s in res[name]["s"]]
+            say(f"  {name:24s} median {np.median(v):9.1f} img/s  min {min(v):9.1f}  max {max(v):9.1f} | entropy "
+                f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+        for q in [int(x) for x in a.queries.split(",") if x]:
+            q = min(q, n)
+            res = passes(q, f"query {q}")
+            say(f"progressive files, cold query of {q} images, GpuJpegSource.get (wall):")
+            for name, *_ in arms:
+                v = [1e3 * s for s in res[name]["s"]]
+                say(f"  {name:24s} median {np.median(v):9.2f} ms  min {min(v):9.2f}  max {max(v):9.2f} | entropy "
+                    f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
 
 
 def main(argv=None) -> int:
@@ -69,6 +153,8 @@ def main(argv=None) -> int:
     ap.add_argument("--par-chunks", default="64,256,1024", help="GpuJpegSource.CHUNK_GPU_PARALLEL values of the sub-stream rows")
     ap.add_argument("--queries", default="64,400", help="sizes of the small cold queries")
     ap.add_argument("--entropy-only", action="store_true", help="only the host / device entropy comparison")
+    ap.add_argument("--progressive", action="store_true",
+                    help="measure progressive files only: progressive='fallback' against 'native' in the three forms")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
 
@@ -89,6 +175,13 @@ def main(argv=None) -> int:
         lines.append(s)
 
     n = a.images
+    if a.progressive:
+        progressive_report(a, dev, say)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return 0
     with tempfile.TemporaryDirectory() as d, torch.cuda.device(dev):
         t0 = time.perf_counter()
         nbytes = make_images(d, n)
