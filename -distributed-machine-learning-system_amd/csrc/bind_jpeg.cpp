@@ -273,12 +273,21 @@ struct JpegHuffPacked {
   bool native_progressive = false;
   torch::Tensor scans, tabs, prog_list;
   int64_t n_prog = 0, nscans = 0, ntabs = 0;
+  // packed with restart_intervals: the baseline entries with a restart interval whose markers the packer
+  // found (gpu == 4) as JpegRstItem[nitems], int32 [nitems, 4] = (entry, byte_begin, mcu_first, index),
+  // for jpeg_entropy_rst_kernel; n_lane keeps counting the gpu == 1 entries only
+  bool restart_intervals = false;
+  torch::Tensor rst_items;
+  int64_t n_rst = 0;
 };
 
 // Parses a list of bytes / None and packs the accepted entries, GIL released.  parallel: lay the
 // entries without restart markers out for the sub-stream kernel (jpeg_entropy_gpu_parallel).
 // native_progressive: progressive files are accepted and laid out for the progressive kernel.
-std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bool native_progressive) {
+// restart_intervals: baseline files with a restart interval get one work item per interval for the
+// interval kernel, in either layout.
+std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bool native_progressive,
+                                               bool restart_intervals) {
   const int n = (int)datas.size();
   std::vector<const uint8_t*> ptr(n, nullptr);
   std::vector<size_t> len(n, 0);
@@ -295,14 +304,16 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   {
     py::gil_scoped_release nogil;
     jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b,
-                   parallel ? kJpegParSubBits : 0u, native_progressive);
+                   parallel ? kJpegParSubBits : 0u, native_progressive, restart_intervals);
   }
   const char* why = parallel ? jpeg_huff_par_check(b.desc.data(), b.par.data(), n, b.byte_total, (int64_t)b.sets.size(),
-                                                   b.coef_total, b.scratch_total, kJpegParSubBits, native_progressive)
+                                                   b.coef_total, b.scratch_total, kJpegParSubBits, native_progressive,
+                                                   restart_intervals)
                              : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total,
-                                               native_progressive);
+                                               native_progressive, restart_intervals);
   if (why == nullptr && native_progressive)
     why = jpeg_huff_prog_check(b.desc.data(), n, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
+  if (why == nullptr) why = jpeg_huff_rst_check(b.desc.data(), n, b.rst_items.data(), (int64_t)b.rst_items.size());
   TORCH_CHECK(why == nullptr, "jpeg_huff_pack: bad descriptor: ", why ? why : "");
   pk->bytes = torch::empty({b.byte_total}, torch::kUInt8);
   pk->sets = torch::empty({(int64_t)(b.sets.size() * sizeof(JpegHuffSet))}, torch::kUInt8);
@@ -318,6 +329,11 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   pk->tabs = torch::empty({(int64_t)(b.tabs.size() * sizeof(JpegHuffTab))}, torch::kUInt8);
   if (!b.scans.empty()) std::memcpy(pk->scans.data_ptr(), b.scans.data(), b.scans.size() * sizeof(JpegProgScan));
   if (!b.tabs.empty()) std::memcpy(pk->tabs.data_ptr(), b.tabs.data(), b.tabs.size() * sizeof(JpegHuffTab));
+  static_assert(sizeof(JpegRstItem) == 4 * sizeof(int32_t), "an item is a row of four int32");
+  pk->restart_intervals = restart_intervals;
+  pk->rst_items = torch::empty({(int64_t)b.rst_items.size(), 4}, torch::kInt32);
+  if (!b.rst_items.empty())
+    std::memcpy(pk->rst_items.data_ptr(), b.rst_items.data(), b.rst_items.size() * sizeof(JpegRstItem));
   std::vector<int32_t> prog_list;
   {
     py::gil_scoped_release nogil;
@@ -332,6 +348,7 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
       pk->offs[i] = b.desc[i].coef_base;
       ++pk->n_gpu;
       if (b.desc[i].gpu == 3) prog_list.push_back(i);
+      else if (b.desc[i].gpu == 4) ++pk->n_rst;
       else ++(b.desc[i].gpu == 2 ? pk->n_par : pk->n_lane);
     }
   pk->n_prog = (int64_t)prog_list.size();
@@ -356,7 +373,9 @@ static void check_entropy_operands(const char* op, const std::shared_ptr<JpegHuf
                   pk->sets.numel() == pk->nsets * (int64_t)sizeof(JpegHuffSet) &&
                   pk->scans.numel() == pk->nscans * (int64_t)sizeof(JpegProgScan) &&
                   pk->tabs.numel() == pk->ntabs * (int64_t)sizeof(JpegHuffTab) && pk->prog_list.numel() == pk->n_prog &&
-                  pk->ntabs < (1ll << 31), op, ": packed batch changed");
+                  pk->ntabs < (1ll << 31) && pk->rst_items.dim() == 2 && pk->rst_items.size(1) == 4 &&
+                  pk->rst_items.is_contiguous() && pk->rst_items.scalar_type() == torch::kInt32 &&
+                  (pk->n_rst > 0) == (pk->rst_items.size(0) > 0), op, ": packed batch changed");
 }
 
 // The progressive entries of a packed batch (gpu == 3), one lane each, into the same coefs / status on
@@ -383,8 +402,29 @@ static void launch_progressive(const char* op, const std::shared_ptr<JpegHuffPac
   check_launch("jpeg_entropy_prog");
 }
 
+// The restart-interval entries of a packed batch (gpu == 4), one lane per interval, into the same coefs /
+// status on the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with allow_rst.
+// The kernel only raises the status of an entry one of whose intervals is refused (atomic max) and writes
+// nothing for an accepted one, so status must be zero on entry: runtime/jpeg.py _entropy_on_device
+// allocates it with torch.zeros, and no other kernel writes the status of a gpu == 4 entry.
+static void launch_restart(const char* op, const std::shared_ptr<JpegHuffPacked>& pk, const torch::Tensor& bytes,
+                           const torch::Tensor& dev_desc, const torch::Tensor& dev_sets, torch::Tensor& coefs,
+                           torch::Tensor& status) {
+  if (pk->n_rst == 0) return;
+  const char* why = jpeg_huff_rst_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
+                                        reinterpret_cast<const JpegRstItem*>(pk->rst_items.data_ptr()),
+                                        pk->rst_items.size(0));
+  TORCH_CHECK(why == nullptr, op, ": restart-interval item outside its entry: ", why ? why : "");
+  auto dev_items = pk->rst_items.to(bytes.device());
+  jpeg_entropy_rst_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr()),
+                          reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()),
+                          reinterpret_cast<const JpegRstItem*>(dev_items.data_ptr()), (int)pk->rst_items.size(0),
+                          coefs.data_ptr<int16_t>(), status.data_ptr<int>(), (int)pk->n, cur_stream());
+  check_launch("jpeg_entropy_rst");
+}
+
 // Decodes the packed batch into coefs (zeroed by the caller: jpeg_entropy_zero) on the current
-// stream; status is written for the accepted entries only.  Every descriptor is checked against
+// stream; status is written for the accepted entries only (zero on entry: see launch_restart).  Every descriptor is checked against
 // these very buffers first.
 void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
                       torch::Tensor status) {
@@ -393,7 +433,8 @@ void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor b
   if (pk->n_gpu == 0) return;
   check_entropy_operands("jpeg_entropy_gpu", pk, bytes, coefs, status);
   const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
-                                    bytes.numel(), pk->nsets, coefs.numel(), pk->native_progressive);
+                                    bytes.numel(), pk->nsets, coefs.numel(), pk->native_progressive,
+                                    pk->restart_intervals);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
@@ -403,6 +444,7 @@ void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor b
                         status.data_ptr<int>(), (int)pk->n, cur_stream());
     check_launch("jpeg_entropy");
   }
+  launch_restart("jpeg_entropy_gpu", pk, bytes, dev_desc, dev_sets, coefs, status);
   launch_progressive("jpeg_entropy_gpu", pk, bytes, dev_desc, coefs, status);
 }
 
@@ -420,7 +462,7 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
   const char* why = jpeg_huff_par_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()),
                                         reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n,
                                         bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits,
-                                        pk->native_progressive);
+                                        pk->native_progressive, pk->restart_intervals);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu_parallel: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
@@ -438,6 +480,7 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
                             reinterpret_cast<uint32_t*>(scratch.data_ptr<int>()), (int)pk->n, cur_stream());
     check_launch("jpeg_entropy_par");
   }
+  launch_restart("jpeg_entropy_gpu_parallel", pk, bytes, dev_desc, dev_sets, coefs, status);
   launch_progressive("jpeg_entropy_gpu_parallel", pk, bytes, dev_desc, coefs, status);
 }
 
@@ -530,11 +573,16 @@ void bind_jpeg(py::module_& m) {
       .def_readonly("native_progressive", &JpegHuffPacked::native_progressive)
       .def_readonly("n_prog", &JpegHuffPacked::n_prog)
       .def_readonly("nscans", &JpegHuffPacked::nscans)
-      .def_readonly("ntabs", &JpegHuffPacked::ntabs);
+      .def_readonly("ntabs", &JpegHuffPacked::ntabs)
+      .def_readonly("restart_intervals", &JpegHuffPacked::restart_intervals)
+      .def_readonly("rst_items", &JpegHuffPacked::rst_items)
+      .def_readonly("n_rst", &JpegHuffPacked::n_rst);
   m.def("jpeg_huff_pack", &jpeg_huff_pack,
         "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage "
-        "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel)",
-        py::arg("datas"), py::arg("parallel") = false, py::arg("native_progressive") = false);
+        "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel; restart_intervals: one work item per "
+        "restart interval for the interval kernel)",
+        py::arg("datas"), py::arg("parallel") = false, py::arg("native_progressive") = false,
+        py::arg("restart_intervals") = false);
   m.attr("JPEG_PROG_MAX_SCANS") = (int64_t)kJpegProgMaxScans;
   m.attr("JPEG_HEADER_PROGRESSIVE_OFFSET") = (int64_t)offsetof(JpegHeader, progressive);   // an int, in the header rows
   m.attr("JPEG_PAR_SUB_BITS") = (int64_t)kJpegParSubBits;

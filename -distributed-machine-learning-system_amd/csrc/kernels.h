@@ -300,5 +300,13 @@ struct JpegProgScan;
 void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int ntabs, const JpegProgScan* scans,
                               long long nscans, const JpegHuffDesc* desc, int n, const int* list, int nlist,
                               int16_t* coef, int* status, hipStream_t st);
+// one lane per item of items[0, nitems), the restart intervals of the batch's gpu == 4 entries
+// (jpeg_huff_rst.h); a lane whose interval is refused raises status[entry] to JPEG_CORRUPT with an atomic
+// max and a lane that accepts writes nothing, so status must be zero on entry.  The caller has run
+// jpeg_huff_check(..., allow_rst) and jpeg_huff_rst_check over desc and items.
+struct JpegRstItem;
+void jpeg_entropy_rst_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
+                             const JpegRstItem* items, int nitems, int16_t* coef, int* status, int n,
+                             hipStream_t st);
 
 }  // namespace idunno

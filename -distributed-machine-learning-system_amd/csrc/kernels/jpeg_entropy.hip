@@ -15,18 +15,22 @@
 //
 // jpeg_entropy_par_kernel (entropy_on="gpu_parallel", further down) decodes one
 // image on a whole workgroup instead.  jpeg_entropy_prog_kernel
-// (progressive="native", last) decodes the progressive files of a batch, one lane
-// per image like the first, in either device form.
+// (progressive="native") decodes the progressive files of a batch, one lane
+// per image like the first, in either device form.  jpeg_entropy_rst_kernel
+// (restart="intervals", last) decodes the baseline files with a restart interval,
+// one lane per interval, in either device form as well.
 //
 // The host (bind_jpeg.cpp jpeg_entropy_gpu / jpeg_entropy_gpu_parallel) has checked every descriptor against
 // the three buffers with jpeg_huff_check before the launch (the progressive entries'
-// scan ranges and table indices with jpeg_huff_prog_check); inside a span the
-// core checks every access itself.
+// scan ranges and table indices with jpeg_huff_prog_check, the restart-interval
+// entries' work items with jpeg_huff_rst_check); inside a span the core checks
+// every access itself.
 #include <hip/hip_runtime.h>
 
 #include "../jpeg_huff_core.h"
 #include "../jpeg_huff_par.h"
 #include "../jpeg_huff_prog.h"
+#include "../jpeg_huff_rst.h"
 #include "../kernels.h"
 
 namespace idunno {
@@ -153,7 +157,41 @@ __global__ __launch_bounds__(64) void jpeg_entropy_prog_kernel(const uint8_t* __
                                      ntabs, coef + d.coef_base);
 }
 
+// Restart-interval files (restart="intervals", gpu == 4): one lane decodes one restart
+// interval with the core of jpeg_huff_rst.h, over the flattened item list of the whole
+// batch, in workgroups of one wave like jpeg_entropy_kernel so that a small batch spreads
+// over the CUs.  The items of one image sit on consecutive lanes, and the core's flat
+// one-symbol-per-trip loop keeps a wave on the same instructions across block and MCU
+// boundaries.  A wave may hold items of several images with different table sets, so the
+// tables stay in global memory as in the one-lane kernel.  Intervals write disjoint
+// blocks of the image's span.  A lane whose interval is refused raises the image's status
+// with an atomic max; a lane that accepts writes nothing, so status is zero on entry (the
+// caller's torch.zeros).  No barrier, no LDS, no lane or workgroup waits for another.
+__global__ __launch_bounds__(64) void jpeg_entropy_rst_kernel(const uint8_t* __restrict__ bytes,
+                                                              const JpegHuffSet* __restrict__ sets,
+                                                              const JpegHuffDesc* __restrict__ desc,
+                                                              const JpegRstItem* __restrict__ items, int nitems,
+                                                              int16_t* __restrict__ coef, int* status, int n) {
+  const long long j = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (j >= nitems) return;
+  const JpegRstItem it = items[j];
+  if (it.entry < 0 || it.entry >= n) return;
+  const JpegHuffDesc& d = desc[it.entry];
+  if (d.gpu != 4) return;
+  const int st = jpeg_huff_decode_interval(d, reinterpret_cast<const uint32_t*>(bytes + d.byte_off), sets[d.set_idx],
+                                           coef + d.coef_base, it.byte_begin, it.mcu_first, it.index);
+  if (st != kJpegHuffOk) atomicMax(&status[it.entry], kJpegHuffCorrupt);
+}
+
 }  // namespace
+
+void jpeg_entropy_rst_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
+                             const JpegRstItem* items, int nitems, int16_t* coef, int* status, int n,
+                             hipStream_t st) {
+  if (nitems <= 0 || n <= 0) return;
+  hipLaunchKernelGGL(jpeg_entropy_rst_kernel, dim3((unsigned)(((long long)nitems + 63) / 64)), dim3(64), 0, st, bytes,
+                     sets, desc, items, nitems, coef, status, n);
+}
 
 void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int ntabs, const JpegProgScan* scans,
                               long long nscans, const JpegHuffDesc* desc, int n, const int* list, int nlist,

@@ -141,11 +141,13 @@ size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 }  // namespace
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive) {
+                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive, bool restart_intervals) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
   out->scans.clear();
   out->tabs.clear();
+  out->rst_items.clear();
+  std::vector<uint32_t> begins;
   std::map<std::string, int> seen_tabs;
   JpegProgScript script;
   out->byte_total = out->coef_total = out->scratch_total = 0;
@@ -254,6 +256,36 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       d.td[c] = rs.td[c];
       d.ta[c] = rs.ta[c];
     }
+    if (restart_intervals && d.gpu == 1 && h.restart_interval > 0 && h.mcux >= 1 && h.mcuy >= 1) {
+      // one item per interval: the byte after each in-sequence RSTn, found by the reader's byte rules
+      const int64_t ri = h.restart_interval;
+      const int64_t need = ((int64_t)h.mcux * h.mcuy + ri - 1) / ri - 1;
+      const uint8_t* s = data[i] + h.scan_pos;
+      const size_t m = len[i] - h.scan_pos;
+      begins.clear();
+      size_t p = 0;
+      while ((int64_t)begins.size() < need && p + 1 < m) {
+        if (s[p] != 0xFFu) {
+          ++p;
+        } else if (s[p + 1] == 0xFFu) {
+          ++p;                          // fill byte: look again from the next FF
+        } else if (s[p + 1] == 0x00u) {
+          p += 2;
+        } else if (s[p + 1] == 0xD0u + (begins.size() & 7u)) {
+          p += 2;
+          begins.push_back((uint32_t)p);
+        } else {
+          break;                        // another marker, or an RSTn out of sequence
+        }
+      }
+      // a marker with nothing behind it starts no interval: left to the one-lane kernel like a missing one
+      const bool found = (int64_t)begins.size() == need && d.byte_len > 0 && (begins.empty() || begins.back() < d.byte_len);
+      if (found && (int64_t)out->rst_items.size() + need + 1 < 0x7FFFFFFFll) {
+        d.gpu = 4;
+        for (int64_t k = 0; k <= need; ++k)
+          out->rst_items.push_back(JpegRstItem{(int32_t)i, k ? begins[(size_t)k - 1] : 0u, (int32_t)(k * ri), (int32_t)k});
+      }
+    }
   }
 }
 
@@ -280,14 +312,15 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 namespace {
 
 const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
-                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog) {
+                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog, bool allow_rst) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
   int64_t scratch_at = 0;
   if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
   for (int i = 0; i < n; ++i) {
     const JpegHuffDesc& d = desc[i];
     if (!d.gpu) continue;
-    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr) && !(d.gpu == 3 && allow_prog)) return "gpu flag";
+    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr) && !(d.gpu == 3 && allow_prog) && !(d.gpu == 4 && allow_rst))
+      return "gpu flag";
     if (d.byte_off < byte_at || d.byte_off % kJpegHuffByteAlign != 0 || d.byte_len > d.byte_span ||
         d.byte_span % kJpegHuffBytePad != 0 || d.byte_off + (int64_t)d.byte_span > byte_cap)
       return "byte span outside the byte buffer";
@@ -308,6 +341,7 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
       co += (int64_t)d.bw[c] * d.bh[c] * 64;
     }
     if (co != (int64_t)d.total_coefs) return "coefficient count";
+    if (d.gpu == 4 && d.restart_interval < 1) return "restart interval";
     if (d.gpu == 2) {
       const JpegParDesc& p = par[i];
       int bpm = 0;
@@ -326,15 +360,15 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
 }  // namespace
 
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog) {
-  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog);
+                            bool allow_prog, bool allow_rst) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst);
 }
 
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog) {
+                                bool allow_prog, bool allow_rst) {
   if (par == nullptr) return "no sub-stream descriptors";
-  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog);
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst);
 }
 
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
@@ -368,6 +402,30 @@ const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProg
       if (s.ss != 0 && (s.ac_tab < 0 || s.ac_tab >= ntabs)) return "AC table index";
     }
   }
+  return nullptr;
+}
+
+const char* jpeg_huff_rst_check(const JpegHuffDesc* desc, int n, const JpegRstItem* items, int64_t nitems) {
+  if (nitems < 0 || nitems >= 0x7FFFFFFFll || (nitems > 0 && items == nullptr)) return "item count";
+  int64_t at = 0;                         // items follow the entries
+  for (int i = 0; i < n; ++i) {
+    const JpegHuffDesc& d = desc[i];
+    if (d.gpu != 4) continue;
+    if (d.restart_interval < 1 || d.mcux < 1 || d.mcuy < 1) return "restart interval";
+    const int64_t ri = d.restart_interval, mcus = (int64_t)d.mcux * d.mcuy;
+    const int64_t count = (mcus + ri - 1) / ri;
+    if (at + count > nitems) return "items of an entry missing";
+    uint32_t begin_at = 0;
+    for (int64_t k = 0; k < count; ++k) {
+      const JpegRstItem& it = items[at + k];
+      if (it.entry != i || (int64_t)it.index != k) return "items not contiguous and ascending";
+      if ((int64_t)it.mcu_first != k * ri || (int64_t)it.mcu_first >= mcus) return "item's first MCU";
+      if (it.byte_begin >= d.byte_len || it.byte_begin < begin_at) return "item's first byte outside the byte span";
+      begin_at = it.byte_begin;
+    }
+    at += count;
+  }
+  if (at != nitems) return "item of an entry that is not a restart-interval entry";
   return nullptr;
 }
 

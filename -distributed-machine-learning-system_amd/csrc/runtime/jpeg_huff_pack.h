@@ -13,6 +13,7 @@
 
 #include "../jpeg_huff_core.h"
 #include "../jpeg_huff_par.h"
+#include "../jpeg_huff_rst.h"
 #include "jpeg_entropy.h"
 
 namespace idunno {
@@ -28,6 +29,8 @@ struct JpegHuffBatch {
   // progressive files (jpeg_huff_plan with native_progressive), else empty
   std::vector<JpegProgScan> scans;  // the scan scripts of the gpu == 3 entries, back to back
   std::vector<JpegHuffTab> tabs;    // the single tables those scans index; identical tables share one entry
+  // restart-interval files (jpeg_huff_plan with restart_intervals), else empty
+  std::vector<JpegRstItem> rst_items;   // one per interval of the gpu == 4 entries, entry by entry, ascending
 };
 
 // Parses every entry (data[i] == nullptr: JPEG_EMPTY) and lays the batch out.
@@ -43,8 +46,19 @@ struct JpegHuffBatch {
 // the file from the first scan's data to the end in the stuffed layout of gpu == 1,
 // and it names a range of out->scans (jpeg_huff_prog.h), whose tables are entries
 // of out->tabs.
+// restart_intervals: an accepted baseline file with a restart interval is scanned once
+// from scan_pos by the byte rules of jpeg_huff_detail::Bits::fill (FF 00 data, FF FF
+// fill, any other FF xx a marker) for the byte offset after each in-sequence RSTn, up to
+// the first other marker, an out-of-sequence RSTn or the end.  With at least
+// ceil(mcux * mcuy / ri) - 1 markers (later ones are ignored, as the serial decoder
+// ignores what follows the last MCU) it gets gpu == 4 in either form: the stuffed layout
+// of gpu == 1 and one JpegRstItem per interval in out->rst_items (jpeg_huff_rst.h); a
+// restart interval of at least the MCU count needs no marker and is one item.  With
+// fewer markers the serial decoder will refuse the file: it keeps gpu == 1 and the
+// one-lane kernel gives the verdict.  gpu == 2 and gpu == 3 entries are untouched.
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits = 0, bool native_progressive = false);
+                    JpegHuffBatch* out, uint32_t par_sub_bits = 0, bool native_progressive = false,
+                    bool restart_intervals = false);
 
 // Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
 // zeroes the padding between them.  A gpu == 2 entry gets its de-stuffed words
@@ -57,15 +71,16 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 // and the layout inside each span is consistent, else what is wrong.  Run before
 // a launch.
 // allow_prog: gpu == 3 entries are taken (spans and frame; their scans: jpeg_huff_prog_check).
+// allow_rst: gpu == 4 entries are taken (spans, frame, a restart interval; their items: jpeg_huff_rst_check).
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog = false);
+                            bool allow_prog = false, bool allow_rst = false);
 
 // The same for a batch planned with par_sub_bits: gpu == 1 entries as above, gpu == 2
 // entries also against their JpegParDesc and the scratch buffer (scratch_cap uint32
 // elements, kJpegParStateWords per sub-stream of sub_bits bits).
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog = false);
+                                bool allow_prog = false, bool allow_rst = false);
 
 // The gpu == 3 entries against the scan buffer (nscans JpegProgScan) and the table
 // buffer (ntabs JpegHuffTab) the progressive kernel will get: every image's scan
@@ -74,5 +89,12 @@ const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par
 // the table buffer.  Run next to jpeg_huff_check(..., allow_prog = true) before a launch.
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
                                  int64_t ntabs);
+
+// The work items of the interval kernel against the descriptors: every item's entry a
+// gpu == 4 entry, byte_begin < byte_len, mcu_first == index * restart_interval <
+// mcux * mcuy; the items of one entry contiguous, ascending and complete (every gpu == 4
+// entry has all ceil(mcux * mcuy / ri) of them, entries ascending); nitems < 2^31.  Run
+// next to jpeg_huff_check(..., allow_rst = true) before a launch.
+const char* jpeg_huff_rst_check(const JpegHuffDesc* desc, int n, const JpegRstItem* items, int64_t nitems);
 
 }  // namespace idunno

@@ -33,7 +33,7 @@ from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
-# (device, directory, entropy_on, progressive) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# (device, directory, entropy_on, progressive, restart) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
 # index only; after replacing files of a directory call drop_gpu_sources()
 _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
@@ -58,7 +58,7 @@ def drop_gpu_sources() -> None:
 def deeplearning(filename: str, modelname: str, start_image: int, end_image: int, *,
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
                  data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host",
-                 progressive: str = "fallback"):
+                 progressive: str = "fallback", restart: str = "lane"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
     ``decoder="gpu"`` decodes the JPEG files with the native entropy decoder and
@@ -69,13 +69,18 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     on host threads, one lane per image, and ``"gpu_parallel"`` does so with one
     workgroup per image; the default is ``"host"``.  ``progressive="native"``
     (with ``decoder="gpu"``) decodes progressive JPEG files natively in that
-    form instead of handing them to Pillow; the default is ``"fallback"``."""
+    form instead of handing them to Pillow; the default is ``"fallback"``.
+    ``restart="intervals"`` (with ``decoder="gpu"`` and a device
+    ``entropy_on``) decodes baseline files with a restart interval one interval
+    per lane instead of on one lane; the default is ``"lane"``."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
     if entropy_on not in ("host", "gpu", "gpu_parallel"):
         raise ValueError(f"entropy_on must be 'host', 'gpu' or 'gpu_parallel', not {entropy_on!r}")
     if progressive not in ("fallback", "native"):
         raise ValueError(f"progressive must be 'fallback' or 'native', not {progressive!r}")
+    if restart not in ("lane", "intervals"):
+        raise ValueError(f"restart must be 'lane' or 'intervals', not {restart!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -87,10 +92,11 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         src = SyntheticSource(data_seed, device)
     elif decoder == "gpu":
         with _LOCK:
-            key = (str(device), os.path.abspath(d), entropy_on, progressive)
+            key = (str(device), os.path.abspath(d), entropy_on, progressive, restart)
             src = _GPU_SOURCES.get(key)
             if src is None:
-                src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on, progressive=progressive)
+                src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on, progressive=progressive,
+                                                              restart=restart)
     else:
         src = JpegSource(device, root=d)
     names = class_names()
@@ -119,9 +125,12 @@ def main(argv=None) -> int:
                          "or on the device with one workgroup per image")
     ap.add_argument("--progressive", default="fallback", choices=["fallback", "native"],
                     help="with --decoder gpu: progressive JPEG files through Pillow, or decoded natively")
+    ap.add_argument("--restart", default="lane", choices=["lane", "intervals"],
+                    help="with --decoder gpu and a device --entropy: a file with restart markers on one lane, or one "
+                         "restart interval per lane")
     a = ap.parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
-                           decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive)
+                           decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive, restart=a.restart)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

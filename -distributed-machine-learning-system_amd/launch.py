@@ -62,7 +62,7 @@ def run_node(a) -> int:
     if a.source == "jpeg":
         # real files: `put` test_<i>.JPEG into SDFS, then `inference <start> <end> <model>`
         node.source = GpuJpegSource(sdfs=node.sdfs, device=dev, entropy_on=a.jpeg_entropy,
-                                    progressive=a.jpeg_progressive)
+                                    progressive=a.jpeg_progressive, restart=a.jpeg_restart)
     else:
         node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
                        else SyntheticSource(cfg.data_seed, dev))
@@ -87,7 +87,8 @@ def run_cluster(a) -> int:
     shell_node = cfg.num_nodes - 1 if a.shell_node is None else a.shell_node
     procs = []
     base = [sys.executable, "-m", "idunno.launch", "node", "--executor", a.executor, "--source", a.source,
-            "--jpeg-entropy", a.jpeg_entropy, "--jpeg-progressive", a.jpeg_progressive]
+            "--jpeg-entropy", a.jpeg_entropy, "--jpeg-progressive", a.jpeg_progressive,
+            "--jpeg-restart", a.jpeg_restart]
     for flag, v in (("--config", a.config), ("--nodes", cfg.num_nodes), ("--base-port", cfg.base_port),
                     ("--store-root", cfg.store_root), ("--log-dir", a.log_dir)):
         if v is not None:
@@ -137,6 +138,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "gpu = one lane per image, gpu_parallel = one workgroup per image")
     ap.add_argument("--jpeg-progressive", default="fallback", choices=["fallback", "native"],
                     help="--source jpeg: progressive files through Pillow, or decoded natively")
+    ap.add_argument("--jpeg-restart", default="lane", choices=["lane", "intervals"],
+                    help="--source jpeg with a device --jpeg-entropy: a file with restart markers on one lane, or one "
+                         "restart interval per lane")
     ap.add_argument("--shell", action="store_true")
     ap.add_argument("--shell-node", type=int, default=None)
     ap.add_argument("--no-shell", action="store_true")

@@ -370,15 +370,21 @@ def __getattr__(name: str):
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = False):
+def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = False,
+                   restart_intervals: bool = False):
     """Parse a list of ``bytes | None`` and pack the accepted entries for the
     device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
     ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
     ``bytes`` (host uint8 tensor, ``byte_total``), ``coef_total``, ``n_gpu``.
     ``native_progressive``: progressive files are packed too (``n_prog``
     entries, one scan descriptor per scan) for the progressive kernel, which
-    ``jpeg_entropy_gpu`` / ``jpeg_entropy_gpu_parallel`` launch next to theirs."""
-    return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive))
+    ``jpeg_entropy_gpu`` / ``jpeg_entropy_gpu_parallel`` launch next to theirs.
+    ``restart_intervals``: baseline files with a restart interval whose
+    ``RSTn`` markers the packer finds (``n_rst`` entries) get one work item per
+    interval in ``rst_items`` (int32 ``[items, 4]``: entry, first byte, first
+    MCU, interval index) for the interval kernel, which the same two calls
+    launch; ``n_lane`` keeps counting the entries of the one-lane kernel."""
+    return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive), bool(restart_intervals))
 
 
 def jpeg_entropy_zero(coefs):

@@ -17,7 +17,7 @@ coefficients (an eighth of the size):
 lanes of a workgroup instead (self-synchronising sub-streams, csrc/jpeg_huff_par.h,
 jpeg_entropy_par_kernel), so a small query no longer waits for one lane to walk
 a whole stream; files with restart markers keep the one-lane kernel in the same
-batch.
+batch (unless ``restart="intervals"``, below).
 
 ``progressive="native"`` (opt-in, default ``"fallback"``) takes progressive
 files in all three forms.  One marker walk over the whole file
@@ -27,6 +27,15 @@ intervals) decodes it scan by scan into the same coefficient layout: on the
 host threads, or on the device with one lane per image (jpeg_entropy_prog_kernel,
 also under ``"gpu_parallel"``: there is no sub-stream form for progressive
 scans).  Everything after the entropy stage is unchanged.
+
+``restart="intervals"`` (opt-in, default ``"lane"``) decodes a baseline file
+with a restart interval one interval per lane in both device forms
+(csrc/jpeg_huff_rst.h, jpeg_entropy_rst_kernel): after every ``RSTn`` the
+reader is byte-aligned, the DC predictors are zero and the MCU number is
+known, so the packer finds the markers with one byte scan and every interval
+is decoded by the serial decoder's own loop from the serial decoder's own
+state.  With ``"lane"`` such a file is walked by one lane of the one-lane
+kernel, whatever the form.
 
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
@@ -63,6 +72,15 @@ def _check_progressive(progressive: str) -> str:
     if progressive not in PROGRESSIVE:
         raise ValueError(f"progressive must be one of {PROGRESSIVE}, not {progressive!r}")
     return progressive
+
+
+RESTART = ("lane", "intervals")
+
+
+def _check_restart(restart: str) -> str:
+    if restart not in RESTART:
+        raise ValueError(f"restart must be one of {RESTART}, not {restart!r}")
+    return restart
 
 
 def parse(data: bytes, progressive: str = "fallback"):
@@ -231,21 +249,25 @@ def _check_entropy_on(entropy_on: str) -> str:
     return entropy_on
 
 
-def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback"):
+def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback",
+                  restart: str = "lane"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
     kernels).  With ``entropy_on="gpu"`` or ``"gpu_parallel"`` it only parses the
     headers and packs bytes, tables and descriptors for the entropy kernels (one
     thread, GIL released as well).  ``progressive="native"`` takes progressive
-    files in either form.  Returns what ``decode_batch(..., entropy=)`` takes;
-    the result remembers both options."""
+    files in either form; ``restart="intervals"`` packs one work item per
+    restart interval for the interval kernel in the two device forms (the host
+    form is unchanged by it).  Returns what ``decode_batch(..., entropy=)``
+    takes; the result remembers the options."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
+    intervals = _check_restart(restart) == "intervals"
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
     if entropy_on in _DEVICE_FORMS:
-        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native)
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals)
         return entropy_on, datas, packed, time.perf_counter() - t0
     status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native)
     return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive
@@ -282,15 +304,18 @@ def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
     return dev_coefs, dev_status, times
 
 
-def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8, progressive: str = "fallback"):
+def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8, progressive: str = "fallback",
+                  restart: str = "lane"):
     """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
     from the host decoder or, with ``entropy_on="gpu"`` / ``"gpu_parallel"`` on a
     GPU ``device``, from the entropy kernels.  ``progressive="native"``:
-    progressive files are decoded too, in every form."""
+    progressive files are decoded too, in every form.  ``restart="intervals"``:
+    the device forms decode restart-interval files one interval per lane."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
+    intervals = _check_restart(restart) == "intervals"
     C = _C()
     datas = [None if d is None else bytes(d) for d in datas]
     if entropy_on == "host":
@@ -301,7 +326,7 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
         raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native)
+    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals)
     status = list(packed.status)
     coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
     if packed.n_gpu:
@@ -318,7 +343,7 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
 
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
                  stager: HbmStager | None = None, entropy=None, entropy_on: str = "host",
-                 progressive: str = "fallback"):
+                 progressive: str = "fallback", restart: str = "lane"):
     """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
     ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
     resized or cropped and the result is a list of [H, W, 3] tensors (``None``
@@ -360,9 +385,24 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     the one asked for, and nothing native runs), ``info["progressive_images"]``
     counts the progressive files decoded natively.  Non-interleaved baseline
     files (``"multiscan"``), arithmetic coding, 12-bit samples and CMYK remain
-    fallbacks."""
+    fallbacks.
+
+    ``restart="intervals"`` (default ``"lane"``: a baseline file with a restart
+    interval is walked by one lane of the one-lane kernel in both device forms)
+    decodes such a file one restart interval per lane
+    (jpeg_entropy_rst_kernel, csrc/jpeg_huff_rst.h) in ``"gpu"`` and
+    ``"gpu_parallel"``; the packer finds the ``RSTn`` markers, and a file that
+    lacks one stays with the one-lane kernel, which refuses it.  An image one of
+    whose intervals is refused is a ``"corrupt"`` fallback like any other.
+    Progressive files with restart markers stay on the progressive kernel.
+    ``info["restart"]`` names the mode in effect (when ``entropy`` was prepared
+    in a device form, the one it was prepared in; on a CPU device and in the
+    host form the one asked for, and nothing changes there),
+    ``info["restart_images"]`` counts the images the interval kernel decoded
+    and did not flag."""
     _check_entropy_on(entropy_on)
     _check_progressive(progressive)
+    _check_restart(restart)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
@@ -374,9 +414,12 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         # the form and the mode the entropy stage was prepared in decide
         datas = entropy[1] if on_gpu else entropy[0]
         progressive = ("native" if entropy[2].native_progressive else "fallback") if on_gpu else entropy[6]
+        if on_gpu:
+            restart = "intervals" if entropy[2].restart_intervals else "lane"
     native = progressive == "native"
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
-            "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0}
+            "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0,
+            "restart": restart, "restart_images": 0}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -396,7 +439,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     packed = None
     if on_gpu:
         _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form,
-                                                                                         progressive)
+                                                                                         progressive, restart)
         status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
     else:
         _, status, hdr, coefs, offs, info["entropy_s"] = (entropy if entropy is not None else
@@ -448,6 +491,9 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                     if status[i] == 0 and st != 0:
                         status[i] = int(st)
                         info["gpu_images"] -= 1
+                if packed.n_rst:
+                    # column 0 of the work items: the entries the interval kernel took
+                    info["restart_images"] = sum(1 for i in set(packed.rst_items[:, 0].tolist()) if status[i] == 0)
             else:
                 info["h2d_s"] = ev[0].elapsed_time(ev[1]) * 1e-3
             info["idct_s"] = ev[2].elapsed_time(ev[3]) * 1e-3

@@ -33,8 +33,17 @@ serial loop) against ``"native"``, for ``entropy_on="host"`` at ``--threads``,
 repetitions after a warm-up of every arm, then the cold query of each
 ``--queries`` size for the same six arms.
 
+``--restart ROWS`` measures restart-interval files instead and nothing else: the
+same images encoded with ``restart_marker_rows=ROWS`` (a restart interval of
+ROWS MCU rows), cold ``GpuJpegSource.get`` passes with ``restart="lane"`` (one
+lane walks the whole stream) against ``"intervals"`` (one lane per restart
+interval), for ``entropy_on="gpu"`` and ``"gpu_parallel"``: four arms
+alternating in one process, ``--reps`` repetitions after a warm-up of every arm,
+then the cold query of each ``--queries`` size for the same four arms.
+
     python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
     python tools/jpeg_bench.py --progressive --queries 64 --out profiles/jpeg_bench_progressive.log
+    python tools/jpeg_bench.py --restart 1 --queries 64,400 --out profiles/jpeg_bench_restart.log
 """
 from __future__ import annotations
 
@@ -51,7 +60,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def make_images(d: str, n: int, seed: int = 0, progressive: bool = False) -> int:
+def make_images(d: str, n: int, seed: int = 0, progressive: bool = False, restart_rows: int = 0) -> int:
     """Smooth structure plus noise: files of a photograph's size (~40-60 KB), not of flat colour."""
     from PIL import Image
 
@@ -64,7 +73,8 @@ def make_images(d: str, n: int, seed: int = 0, progressive: bool = False) -> int
         a = np.stack([127.5 + 90 * np.sin(xx / fx[c] + ph[c]) * np.cos(yy / fy[c] + ph[3 + c]) for c in range(3)], 2)
         a = np.clip(a + rng.normal(0, 12, a.shape), 0, 255).astype(np.uint8)
         p = os.path.join(d, f"test_{i}.JPEG")
-        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2, progressive=progressive)
+        kw = {"restart_marker_rows": restart_rows} if restart_rows else {}
+        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2, progressive=progressive, **kw)
         total += os.path.getsize(p)
     return total
 
@@ -144,6 +154,75 @@ def progressive_report(a, dev, say) -> None:
                     f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
 
 
+def restart_report(a, dev, say) -> None:
+    """``--restart ROWS``: one lane per file against one lane per restart interval, four arms."""
+    import torch
+
+    from idunno.runtime.data import GpuJpegSource
+
+    n = a.images
+    arms = [(f"{on:12s} {mode}", on, mode) for on in ("gpu", "gpu_parallel") for mode in ("lane", "intervals")]
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        x = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, x
+
+    with tempfile.TemporaryDirectory() as d, torch.cuda.device(dev):
+        t0 = time.perf_counter()
+        nbytes = make_images(d, n, restart_rows=a.restart)
+        say(f"{n} images 500x375 4:2:0 q90 with restart_marker_rows={a.restart} "
+            f"({-(-24 // a.restart)} restart intervals each), {nbytes / n / 1024:.1f} KiB each, generated in "
+            f"{time.perf_counter() - t0:.1f} s; {torch.cuda.get_device_name(0)}")
+
+        def source(on, mode):
+            return GpuJpegSource(dev, root=d, threads=a.threads, entropy_on=on, restart=mode)
+
+        def passes(q, label):
+            want = GpuJpegSource(dev, root=d, threads=a.threads).get(0, q - 1)      # the host form
+            for _, on, mode in arms:                                # warm-up of every arm; the outputs must agree
+                src = source(on, mode)
+                assert torch.equal(src.get(0, q - 1), want), (on, mode)
+                assert src.fallbacks == 0 and src.restart_images == (q if mode == "intervals" else 0), (on, mode)
+            del want
+            res = {name: {"s": [], "entropy_s": [], "cpu_s": []} for name, *_ in arms}
+            for r in range(a.reps):
+                for name, on, mode in arms:
+                    src = source(on, mode)
+                    c0 = time.process_time()
+                    dt, y = timed(lambda: src.get(0, q - 1))
+                    cpu = time.process_time() - c0
+                    assert src.decoded == q and src.fallbacks == 0
+                    res[name]["s"].append(dt)
+                    res[name]["entropy_s"].append(src.seconds["entropy_s"])
+                    res[name]["cpu_s"].append(cpu)
+                    say(f"{label} rep {r}: {name:24s} {1e3 * dt:10.2f} ms  {q / dt:9.1f} img/s  entropy "
+                        f"{1e3 * src.seconds['entropy_s']:9.2f} ms  host CPU {cpu:7.3f} s")
+                    del y, src
+            return res
+
+        res = passes(n, "full pass")
+        say(f"restart-interval files, cold GpuJpegSource.get of {n} images (entropy: device events of the kernels):")
+        for name, *_ in arms:
+            v = [n / s for s in res[name]["s"]]
+            say(f"  {name:24s} median {np.median(v):9.1f} img/s  min {min(v):9.1f}  max {max(v):9.1f} | entropy "
+                f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+        for q in [int(x) for x in a.queries.split(",") if x]:
+            q = min(q, n)
+            res = passes(q, f"query {q}")
+            say(f"restart-interval files, cold query of {q} images, GpuJpegSource.get (wall):")
+            for name, *_ in arms:
+                v = [1e3 * s for s in res[name]["s"]]
+                say(f"  {name:24s} median {np.median(v):9.2f} ms  min {min(v):9.2f}  max {max(v):9.2f} | entropy "
+                    f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms ({1e6 * np.median(res[name]['entropy_s']) / q:7.1f} "
+                    f"us/image) | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+            for on in ("gpu", "gpu_parallel"):
+                lane, iv = (np.median(res[f"{on:12s} {mode}"]["s"]) for mode in ("lane", "intervals"))
+                say(f"  {on}: lane / intervals = {lane / iv:.2f}x (medians)")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--images", type=int, default=2000)
@@ -155,6 +234,9 @@ def main(argv=None) -> int:
     ap.add_argument("--entropy-only", action="store_true", help="only the host / device entropy comparison")
     ap.add_argument("--progressive", action="store_true",
                     help="measure progressive files only: progressive='fallback' against 'native' in the three forms")
+    ap.add_argument("--restart", type=int, default=0, metavar="ROWS", nargs="?", const=1,
+                    help="measure restart-interval files only (restart_marker_rows=ROWS, default 1): restart='lane' "
+                         "against 'intervals' in the two device forms")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
 
@@ -175,8 +257,10 @@ def main(argv=None) -> int:
         lines.append(s)
 
     n = a.images
-    if a.progressive:
-        progressive_report(a, dev, say)
+    if a.progressive or a.restart:
+        if a.restart < 0 or (a.progressive and a.restart):
+            ap.error("--restart takes a positive number of MCU rows and does not combine with --progressive")
+        (progressive_report if a.progressive else restart_report)(a, dev, say)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
