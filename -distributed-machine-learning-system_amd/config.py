@@ -37,6 +37,8 @@ class ClusterConfig:
     quick_start_wait_s: float = 0.005        # worker: wait this long for a just-queued prefetch before
                                              # answering the finished chunk first
     model_seed: int = 0
+    weights: dict = field(default_factory=dict)   # canonical model name -> checkpoint file (every node of the
+                                             # host reads the same file); models absent keep model_seed
     data_seed: int = 1234
 
     # -- membership / failure detector ----------------------------------------

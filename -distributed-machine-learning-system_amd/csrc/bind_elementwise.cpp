@@ -1,4 +1,4 @@
-// Memory-bound ops and small utilities: pools, softmax_top1, synth_images, graph_launch, tile pickers.
+// Memory-bound ops and small utilities: pools, softmax_top1 / softmax_topk, synth_images, graph_launch, tile pickers.
 #include "binding_util.h"
 
 using namespace idunno;
@@ -72,6 +72,29 @@ std::vector<torch::Tensor> softmax_top1(torch::Tensor logits, c10::optional<torc
   if (rows) softmax_top1_launch(logits.data_ptr<float>(), ld, N, rows, cls.data_ptr<int>(), prob.data_ptr<float>(),
                                 pk, of, cur_stream());
   check_launch("softmax_top1");
+  return {cls, prob};
+}
+
+// (cls int32 [rows, k], prob fp32 [rows, k]) of fp32 logits [rows, N] (row stride >= N, unit
+// column stride): the k best classes of each row in stable descending order.
+std::vector<torch::Tensor> softmax_topk(torch::Tensor logits, int64_t k, c10::optional<torch::Tensor> ovf) {
+  const auto dev = logits.device();
+  check_operand(logits, "logits", torch::kFloat, 2, dev, false);
+  TORCH_CHECK(logits.stride(1) == 1, "logits must be [rows, N] with unit column stride");
+  const int rows = logits.size(0), N = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(rows <= 1 || ld >= N, "logits rows must not overlap (row stride ", ld, " < N ", N, ")");
+  TORCH_CHECK(k >= 1 && k <= 16 && k <= N, "k must be in [1, min(N, 16)], got k = ", k, " for N = ", N);
+  auto cls = torch::empty({rows, k}, logits.options().dtype(torch::kInt));
+  auto prob = torch::empty({rows, k}, logits.options());
+  const int* of = nullptr;
+  if (ovf.has_value() && ovf->defined()) {
+    check_operand(*ovf, "ovf", torch::kInt, -1, dev, false);
+    TORCH_CHECK(ovf->numel() >= 1, "ovf must be an int32 flag on the logits device");
+    of = ovf->data_ptr<int>();
+  }
+  if (rows) softmax_topk_launch(logits.data_ptr<float>(), ld, N, rows, (int)k, cls.data_ptr<int>(),
+                                prob.data_ptr<float>(), of, cur_stream());
+  check_launch("softmax_topk");
   return {cls, prob};
 }
 

@@ -73,6 +73,7 @@ Tensor resize_crop(Tensor img, int64_t resize, int64_t crop);
 Tensor maxpool2d_nhwc(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out);
 Tensor global_avgpool_nhwc(Tensor x);
 std::vector<Tensor> softmax_top1(Tensor logits, OptTensor packed, OptTensor ovf);
+std::vector<Tensor> softmax_topk(Tensor logits, int64_t k, OptTensor ovf);
 void graph_launch(int64_t exec);
 Tensor synth_images(int64_t seed, int64_t start, int64_t n, int64_t hw, torch::Device dev);
 int64_t pick_tile(int64_t M, int64_t Cout);
@@ -188,6 +189,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("global_avgpool_nhwc", &global_avgpool_nhwc, "NHWC global average pool");
   m.def("softmax_top1", &softmax_top1, "fused row softmax + argmax; a set ``ovf`` flag marks every row -2",
         py::arg("logits"), py::arg("packed") = py::none(), py::arg("ovf") = py::none());
+  m.def("softmax_topk", &softmax_topk,
+        "fused row softmax + the k best classes in stable descending order; a set ``ovf`` flag marks every entry -2",
+        py::arg("logits"), py::arg("k"), py::arg("ovf") = py::none());
   m.def("set_split_guard", &set_split_guard,
         "split range guard flag (int32 device tensor) for this thread's split launches; None = off",
         py::arg("flag") = py::none());

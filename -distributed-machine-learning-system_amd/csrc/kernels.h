@@ -245,6 +245,10 @@ void splitk_reduce_launch(const float* part, int S, long MN, int N, const float*
 // ovf (or nullptr): a set split range guard marks every row class -2, prob 0 (rerun on the f32 path)
 void softmax_top1_launch(const float* logits, int ld, int N, int rows, int* cls, float* prob, int* packed,
                          const int* ovf, hipStream_t st);
+// top-k of the row softmax, 1 <= k <= min(N, 16): cls / prob [rows, k], entry j the j-th element of a
+// stable descending sort; column 0 is softmax_top1's result bit for bit; ovf as above, for every entry
+void softmax_topk_launch(const float* logits, int ld, int N, int rows, int k, int* cls, float* prob,
+                         const int* ovf, hipStream_t st);
 
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has

@@ -402,6 +402,137 @@ void softmax_top1_launch(const float* logits, int ld, int N, int rows, int* cls,
                      prob, packed, ovf);
 }
 
+// Row softmax + top-k (1 <= k <= 16, k <= N): one 64-lane wave per row, like
+// softmax_top1_kernel, and column 0 is that kernel's result bit for bit (the same
+// loads, the same max/argmax, the same summation order, p0 = 1 / s).  Entry j is
+// the j-th element of a stable descending sort of the row (value descending, then
+// index ascending): round j takes the best element strictly AFTER round j-1's
+// winner in that total order, so nothing is masked out and -inf entries follow
+// the finite ones in index order at probability exp(-inf) / s = 0.  A NaN never
+// compares as a candidate (as in the top-1 kernel); a row that runs out of
+// candidates that way gets index 0x7fffffff, the top-1 kernel's own "none".
+// cls / prob are [rows, k] row-major.
+__device__ __forceinline__ bool topk_after(float v, int i, float pv, int pi) {
+  return v < pv || (v == pv && i > pi);
+}
+
+__global__ void softmax_topk_kernel(const float* __restrict__ logits, int ld, int N, int rows, int k,
+                                    int* __restrict__ cls, float* __restrict__ prob,
+                                    const int* __restrict__ ovf) {
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= rows) return;
+  int* crow = cls + (size_t)wave * k;
+  float* prow = prob + (size_t)wave * k;
+  if (ovf != nullptr && *ovf != 0) {        // split range exceeded somewhere in this forward
+    if (lane < k) {
+      crow[lane] = -2;
+      prow[lane] = 0.f;
+    }
+    return;
+  }
+  const float* r = logits + (size_t)wave * ld;
+  float best = -INFINITY;
+  int bidx = 0x7fffffff;
+  constexpr int NR = 16;
+  float vr[NR];
+  const bool reg = N <= 64 * NR;
+  if (reg) {
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      const int j = lane + 64 * q;
+      vr[q] = j < N ? r[j] : -INFINITY;
+    }
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+      if (vr[q] > best) {          // strict: the lowest index of a lane wins ties
+        best = vr[q];
+        bidx = lane + 64 * q;
+      }
+  } else {
+    for (int j = lane; j < N; j += 64) {
+      const float v = r[j];
+      if (v > best) {
+        best = v;
+        bidx = j;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bidx, o, 64);
+    if (ov > best || (ov == best && oi < bidx)) {
+      best = ov;
+      bidx = oi;
+    }
+  }
+  float s = 0.f;
+  if (reg) {
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+      if (lane + 64 * q < N) s += __expf(vr[q] - best);
+  } else {
+    for (int j = lane; j < N; j += 64) s += __expf(r[j] - best);
+  }
+  s = wave_sum(s);
+  if (lane == 0) {
+    crow[0] = bidx;
+    prow[0] = 1.f / s;
+  }
+  const float top = best;
+  float pv = best;       // the previous round's winner
+  int pi = bidx;
+  for (int t = 1; t < k; ++t) {
+    float cv = -INFINITY;
+    int ci = 0x7fffffff;
+    bool have = false;     // a -inf entry is a candidate too: the value alone cannot say "none yet"
+    if (reg) {
+#pragma unroll
+      for (int q = 0; q < NR; ++q) {
+        const int j = lane + 64 * q;      // ascending: the lowest index of a lane wins ties
+        if (j < N && topk_after(vr[q], j, pv, pi) && (!have || vr[q] > cv)) {
+          cv = vr[q];
+          ci = j;
+          have = true;
+        }
+      }
+    } else {
+      for (int j = lane; j < N; j += 64) {
+        const float v = r[j];
+        if (topk_after(v, j, pv, pi) && (!have || v > cv)) {
+          cv = v;
+          ci = j;
+          have = true;
+        }
+      }
+    }
+    // a lane without a candidate holds (-inf, 0x7fffffff): it loses to any real entry on the index
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(cv, o, 64);
+      const int oi = __shfl_xor(ci, o, 64);
+      if (ov > cv || (ov == cv && oi < ci)) {
+        cv = ov;
+        ci = oi;
+      }
+    }
+    if (lane == 0) {
+      crow[t] = ci;
+      prow[t] = expf(cv - top) / s;
+    }
+    pv = cv;
+    pi = ci;
+  }
+}
+
+void softmax_topk_launch(const float* logits, int ld, int N, int rows, int k, int* cls, float* prob,
+                         const int* ovf, hipStream_t st) {
+  const int bs = 256;  // 4 rows per block
+  const int grid = (rows + 3) / 4;
+  hipLaunchKernelGGL(softmax_topk_kernel, dim3(grid), dim3(bs), 0, st, logits, ld, N, rows, k, cls, prob, ovf);
+}
+
 // Deterministic synthetic images: byte group g (8 bytes) of image `idx` is the
 // little-endian splitmix64 hash of (seed << 32) ^ (idx * 18816 + g), where
 // 18816 = 224*224*3 / 8.  The CPU generator (idunno.runtime.data) computes the

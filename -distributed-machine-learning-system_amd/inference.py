@@ -7,7 +7,8 @@
 
 Differences from the reference, all deliberate:
   * the model is built once per (model, device) and cached, not re-loaded from
-    torch.hub on every call (A6); weights are random-init (no network);
+    torch.hub on every call (A6); weights are random-init unless ``weights``
+    names a checkpoint file on disk (nothing is downloaded);
   * images ``./<filename>/test_<i>.JPEG`` are decoded in memory and never
     rewritten on disk (A14); when the directory does not exist the
     deterministic synthetic 224x224x3 dataset of the cluster is used instead;
@@ -27,6 +28,7 @@ import time
 
 import torch
 
+from .models.checkpoint import file_key
 from .models.reference import canonical
 from .runtime.data import GpuJpegSource, JpegSource, SyntheticSource
 from .runtime.executor import HipExecutor, TorchExecutor
@@ -39,12 +41,17 @@ _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
 
 
-def _executor(device: torch.device, seed: int):
-    key = (str(device), seed)
+def _executor(device: torch.device, seed: int, model: str | None = None, weights=None):
+    if weights is None:
+        key, wmap = (str(device), seed), None
+    else:
+        # (abspath, size, mtime_ns): a replaced checkpoint file gets a fresh executor
+        key, wmap = (str(device), seed, model, file_key(weights)), {model: os.fspath(weights)}
     with _LOCK:
         ex = _EXECUTORS.get(key)
         if ex is None:
-            ex = HipExecutor(device, seed=seed) if device.type == "cuda" else TorchExecutor(device, seed=seed)
+            ex = (HipExecutor(device, seed=seed, weights=wmap) if device.type == "cuda"
+                  else TorchExecutor(device, seed=seed, weights=wmap))
             _EXECUTORS[key] = ex
     return ex
 
@@ -58,9 +65,18 @@ def drop_gpu_sources() -> None:
 def deeplearning(filename: str, modelname: str, start_image: int, end_image: int, *,
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
                  data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host",
-                 progressive: str = "fallback", restart: str = "lane"):
+                 progressive: str = "fallback", restart: str = "lane", topk: int = 1, weights=None,
+                 classes: str | None = None):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
+    ``topk`` > 1 (at most 16) returns ``(image_name, (cat_1..cat_k),
+    (p_1..p_k))`` per image instead: the k most probable categories, most
+    probable first, equal probabilities in class order.  ``weights`` is a
+    checkpoint file for ``modelname`` (``.safetensors``, or a ``torch.save``d
+    state dict read weights-only; torchvision's parameter names, 1000 classes);
+    a file replaced on disk is loaded again.  ``classes`` is a file of category
+    names, one per line (default: ``$IDUNNO_CLASSES``, else ``class_<i>``).
+    Without ``weights`` the parameters are random-init from ``seed``.
     ``decoder="gpu"`` decodes the JPEG files with the native entropy decoder and
     the HIP kernels (``GpuJpegSource``: decoded images stay in HBM across calls
     by index -- ``drop_gpu_sources()`` after replacing files; without a GPU it
@@ -81,12 +97,14 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         raise ValueError(f"progressive must be 'fallback' or 'native', not {progressive!r}")
     if restart not in ("lane", "intervals"):
         raise ValueError(f"restart must be 'lane' or 'intervals', not {restart!r}")
+    if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 16:
+        raise ValueError(f"topk must be an integer in [1, 16], not {topk!r}")
     t0 = time.time()
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     device = torch.device(device)
     model = canonical(modelname)
-    ex = _executor(device, seed)
+    ex = _executor(device, seed, model, weights)
     d = os.path.join(root, filename)
     if not os.path.isdir(d):
         src = SyntheticSource(data_seed, device)
@@ -99,18 +117,23 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
                                                               restart=restart)
     else:
         src = JpegSource(device, root=d)
-    names = class_names()
+    names = class_names(path=classes)
     n = end_image - start_image + 1
     batch = n if not batch or batch <= 0 else batch
     out = []
     for s in range(start_image, end_image + 1, batch):
         e = min(s + batch - 1, end_image)
+        if topk > 1:
+            cls, prob = ex.run(model, src.get(s, e), s, e, topk=topk)
+            out += [(f"test_{s + i}.JPEG", tuple(names[int(c)] for c in cs), tuple(float(p) for p in ps))
+                    for i, (cs, ps) in enumerate(zip(cls, prob))]
+            continue
         cls, prob = ex.run(model, src.get(s, e), s, e)
         out += [(f"test_{s + i}.JPEG", names[int(c)], float(p)) for i, (c, p) in enumerate(zip(cls, prob))]
     return out, time.time() - t0
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="one-process inference over test_<i>.JPEG (or synthetic) images")
     ap.add_argument("model", help="alexnet | resnet18 | resnet | resnet34 | resnet50")
     ap.add_argument("start", type=int)
@@ -128,9 +151,18 @@ def main(argv=None) -> int:
     ap.add_argument("--restart", default="lane", choices=["lane", "intervals"],
                     help="with --decoder gpu and a device --entropy: a file with restart markers on one lane, or one "
                          "restart interval per lane")
-    a = ap.parse_args(argv)
+    ap.add_argument("--topk", type=int, default=1, help="categories per image, most probable first (1..16)")
+    ap.add_argument("--weights", default=None,
+                    help="checkpoint file for the model (.safetensors or a torch.save'd state dict); default random-init")
+    ap.add_argument("--classes", default=None, help="file of category names, one per line")
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
-                           decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive, restart=a.restart)
+                           decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive, restart=a.restart,
+                           topk=a.topk, weights=a.weights, classes=a.classes)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

@@ -27,7 +27,23 @@ def _cfg(a):
 
     over = {"num_nodes": a.nodes, "base_port": a.base_port, "store_root": a.store_root,
             "log_dir": a.log_dir, "coordinator": a.coordinator, "standby": a.standby}
-    return ClusterConfig.load(a.config, **{k: v for k, v in over.items() if v is not None})
+    cfg = ClusterConfig.load(a.config, **{k: v for k, v in over.items() if v is not None})
+    if getattr(a, "weights", None):
+        cfg.weights = {**cfg.weights, **parse_weights(a.weights)}
+    return cfg
+
+
+def parse_weights(items) -> dict:
+    """``["resnet18=/path/r18.pth", ...]`` -> {canonical model name: absolute path}."""
+    from .models.reference import canonical
+
+    out = {}
+    for it in items or []:
+        model, sep, path = it.partition("=")
+        if not sep or not model or not path:
+            raise ValueError(f"--weights takes MODEL=PATH, got {it!r}")
+        out[canonical(model)] = os.path.abspath(path)
+    return out
 
 
 def run_node(a) -> int:
@@ -51,7 +67,7 @@ def run_node(a) -> int:
     else:
         dev = torch.device("cpu")
     ex = make_executor(a.executor, dev if dev.type == "cuda" else None, seed=cfg.model_seed, dtype=cfg.dtype,
-                       fp32_impl=cfg.fp32_impl)
+                       fp32_impl=cfg.fp32_impl, weights=cfg.weights)
     if cfg.collective_rounds is None:
         # one node per process and per GPU: queries run as RCCL rounds by default
         # (RCCL needs a distinct GPU per rank; nodes sharing a GPU use the TCP path)
@@ -93,6 +109,8 @@ def run_cluster(a) -> int:
                     ("--store-root", cfg.store_root), ("--log-dir", a.log_dir)):
         if v is not None:
             base += [flag, str(v)]
+    for w in a.weights or []:
+        base += ["--weights", w]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for i in range(cfg.num_nodes):
@@ -141,6 +159,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--jpeg-restart", default="lane", choices=["lane", "intervals"],
                     help="--source jpeg with a device --jpeg-entropy: a file with restart markers on one lane, or one "
                          "restart interval per lane")
+    ap.add_argument("--weights", action="append", default=None, metavar="MODEL=PATH",
+                    help="checkpoint file for a model (repeatable); every node reads the same file")
     ap.add_argument("--shell", action="store_true")
     ap.add_argument("--shell-node", type=int, default=None)
     ap.add_argument("--no-shell", action="store_true")

@@ -498,8 +498,16 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
-def build_program(name: str, seed: int = 0, randomize_bn: bool = False, dtype: str = "fp16") -> Program:
+def build_program(name: str, seed: int = 0, randomize_bn: bool = False, dtype: str = "fp16",
+                  weights=None) -> Program:
+    """Program of the named architecture.  ``weights`` (a checkpoint path or a
+    state dict, see ``models.checkpoint``) supplies the parameters; without it
+    they are random-init from ``seed`` (which ``weights`` makes irrelevant)."""
     name = ref.canonical(name)
+    if weights is not None:
+        from .checkpoint import load_model
+
+        return compile_model(load_model(name, weights), name, dtype)
     return compile_model(ref.build(name, seed=seed, randomize_bn=randomize_bn), name, dtype)
 
 
@@ -1003,13 +1011,28 @@ class HipRunner:
             torch.cuda.current_stream(x.device).wait_stream(join)
         return self._conv(blk.convs[-1], y, residual=idt, out=out)
 
-    def _capture_key(self, batch: int, packed=None, slot: int = 0):
+    def _capture_key(self, batch: int, packed=None, slot: int = 0, topk: int | None = None):
+        if topk is not None:        # its own graphs; topk=None keeps the key it always had
+            return (("topk", int(topk), batch, slot), self._variant())
         return ((batch if slot == 0 else (batch, slot)) if packed is None else ("pk", batch, packed.data_ptr()),
                 self._variant())
 
-    def has_graph(self, batch: int, packed=None, slot: int = 0) -> bool:
-        """Whether ``capture(batch, packed=, slot=)`` would replay an existing graph."""
-        return self._capture_key(batch, packed, slot) in self._graphs
+    def has_graph(self, batch: int, packed=None, slot: int = 0, topk: int | None = None) -> bool:
+        """Whether ``capture(batch, packed=, slot=, topk=)`` would replay an existing graph."""
+        return self._capture_key(batch, packed, slot, self._check_topk(topk, packed)) in self._graphs
+
+    def _check_topk(self, topk, packed=None):
+        """``topk`` as an int (or None).  The packed (RCCL round) format stays top-1 pairs."""
+        if topk is None:
+            return None
+        if isinstance(topk, bool) or int(topk) != topk:
+            raise ValueError(f"topk must be an integer or None, got {topk!r}")
+        topk = int(topk)
+        if packed is not None:
+            raise ValueError("topk and packed cannot be combined: the packed result format is top-1 pairs")
+        if not 1 <= topk <= min(16, self.p.num_classes):
+            raise ValueError(f"topk must be in [1, {min(16, self.p.num_classes)}], got {topk}")
+        return topk
 
     def _variant(self) -> tuple:
         """Kernel-choice switches a captured graph depends on (part of its cache key)."""
@@ -1250,10 +1273,15 @@ class HipRunner:
         return out
 
     def forward(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
-                start_offset: int = 0, packed: torch.Tensor | None = None):
+                start_offset: int = 0, packed: torch.Tensor | None = None, topk: int | None = None):
         """(class int32 [B], prob fp32 [B]); with ``packed`` the fused
-        softmax-top1 also writes (class, prob bits) pairs into it."""
+        softmax-top1 also writes (class, prob bits) pairs into it.  An integer
+        ``topk`` returns [B, topk] tensors instead (``ops.softmax_topk``: stable
+        descending order, column 0 the top-1 result); not together with ``packed``."""
+        topk = self._check_topk(topk, packed)
         z = self.logits(img_u8, start, batch, start_offset)
+        if topk is not None:
+            return self.ops.softmax_topk(z, topk, self._ovf if self._guarded() else None)
         return self.ops.softmax_top1(z, packed, self._ovf if self._guarded() else None)
 
     __call__ = forward
@@ -1265,7 +1293,7 @@ class HipRunner:
         return key in self._graphs
 
     def capture_window(self, shard: torch.Tensor, batch: int, start: torch.Tensor | None = None,
-                       start_offset: int = 0, packed: torch.Tensor | None = None):
+                       start_offset: int = 0, packed: torch.Tensor | None = None, topk: int | None = None):
         """hipGraph of forward over a device-side window of ``shard``.
 
         Returns (start, replay): write the first image index into the int64
@@ -1275,7 +1303,10 @@ class HipRunner:
         ``start`` (e.g. the start field of this rank's row of the broadcast
         descriptor table) is read in place, minus ``start_offset``; with
         ``packed`` the graph also writes (class, prob bits) pairs there (the
-        gather's send buffer)."""
+        gather's send buffer).  Window graphs serve the collective rounds,
+        whose result format is top-1 pairs: an integer ``topk`` is refused."""
+        if topk is not None:
+            raise ValueError("capture_window has no top-k form: window graphs write the rounds' top-1 pairs")
         key = ("win", shard.data_ptr(), tuple(shard.shape), batch,
                None if start is None else start.data_ptr(), start_offset,
                None if packed is None else packed.data_ptr(), self._variant())
@@ -1337,13 +1368,16 @@ class HipRunner:
             gc.collect()
 
     # -- hipGraph -------------------------------------------------------------
-    def capture(self, batch: int, hw: int = 224, packed: torch.Tensor | None = None, slot: int = 0):
+    def capture(self, batch: int, hw: int = 224, packed: torch.Tensor | None = None, slot: int = 0,
+                topk: int | None = None):
         """Capture forward for a fixed batch; returns (static_in, replay_fn).
         With ``packed`` the graph also writes (class, prob bits) pairs into
         that caller-owned buffer (e.g. a collective round's send buffer).
         ``slot`` > 0 captures an independent copy (own static buffers), so two
-        forwards of the same batch size can be in flight."""
-        key = self._capture_key(batch, packed, slot)
+        forwards of the same batch size can be in flight.  An integer ``topk``
+        captures its own graph, whose replay returns [batch, topk] tensors."""
+        topk = self._check_topk(topk, packed)
+        key = self._capture_key(batch, packed, slot, topk)
         if key in self._graphs:
             g, sin, sout = self._graphs[key]
             return sin, self._replayer(g, sout, packed)
@@ -1355,7 +1389,7 @@ class HipRunner:
                 self._capturing = True
                 try:
                     for _ in range(2):
-                        self.forward(sin, packed=packed)
+                        self.forward(sin, packed=packed, topk=topk)
                 finally:
                     self._capturing = False
             torch.cuda.current_stream(self.device).wait_stream(s)
@@ -1363,7 +1397,7 @@ class HipRunner:
             self._capturing = True
             try:
                 with _capture_nosync(g, self.device, self.graph_pool):
-                    sout = self.forward(sin, packed=packed)
+                    sout = self.forward(sin, packed=packed, topk=topk)
             finally:
                 self._capturing = False
         self._graphs[key] = (g, sin, sout)

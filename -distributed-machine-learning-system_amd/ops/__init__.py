@@ -11,7 +11,7 @@ from ._ext import available, load, so_path
 
 __all__ = [
     "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
-    "maxpool2d", "global_avgpool", "softmax_top1", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
+    "maxpool2d", "global_avgpool", "softmax_top1", "softmax_topk", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
@@ -314,7 +314,18 @@ def softmax_top1(logits, packed=None, ovf=None):
     return cls, prob
 
 
-OVERFLOW_CLASS = -2      # softmax_top1's mark: a split activation left fp16's range
+def softmax_topk(logits, k: int, ovf=None):
+    """Returns (class int32 [B, k], probability fp32 [B, k]) of fp32 logits
+    [B, N], 1 <= k <= min(N, 16): entry j of a row is the j-th element of a
+    stable descending sort (value descending, then index ascending -- not
+    ``torch.topk``'s tie order), -inf entries last at probability 0.  Column 0
+    is ``softmax_top1`` bit for bit.  A set split range-guard flag ``ovf``
+    marks every entry class -2 (OVERFLOW_CLASS)."""
+    cls, prob = load().softmax_topk(logits, int(k), ovf)
+    return cls, prob
+
+
+OVERFLOW_CLASS = -2      # softmax_top1 / softmax_topk's mark: a split activation left fp16's range
 
 
 def set_split_guard(flag=None):

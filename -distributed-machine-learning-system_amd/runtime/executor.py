@@ -10,7 +10,14 @@ once, BN-folded, in HBM) and runs the whole chunk as one batch:
   * ``TorchExecutor`` fp32 PyTorch reference modules (CPU hosts, tests);
   * ``FakeExecutor``  deterministic answers from the image index, no compute
                       (control-plane tests).
-All return ``(cls int32 [n], prob float32 [n])`` numpy arrays.
+All return ``(cls int32 [n], prob float32 [n])`` numpy arrays; ``run`` /
+``submit`` with an integer ``topk`` (HipExecutor, TorchExecutor) return
+``[n, topk]`` arrays instead: the k best classes of each image in stable
+descending order (value descending, then class index ascending).
+
+``weights`` (HipExecutor, TorchExecutor, make_executor) maps canonical model
+names to checkpoint files (``models.checkpoint``); models absent from it keep
+their random-init parameters from ``seed``.
 """
 from __future__ import annotations
 
@@ -25,6 +32,34 @@ from ..models import reference as ref
 from .data import is_resident
 
 log = logging.getLogger("idunno.executor")
+
+
+def _weights_map(weights) -> dict:
+    """``weights`` with canonical model names as keys."""
+    if not weights:
+        return {}
+    if not isinstance(weights, dict):
+        raise ValueError("weights must map model names to checkpoint paths, e.g. {'resnet18': 'resnet18.pth'}")
+    return {ref.canonical(k): v for k, v in weights.items()}
+
+
+def _log_digest(model: str, module, source) -> None:
+    from ..models.checkpoint import state_digest
+
+    log.warning("%s: serving checkpoint %s, state sha256 %s", model, source if isinstance(source, str) else "<dict>",
+                state_digest(module))
+
+
+def stable_topk(logits: torch.Tensor, k: int):
+    """(cls int32 [n, k], prob [n, k]) of logits [n, N]: the first ``k`` of a
+    stable descending sort of each row (ties to the lower index; ``torch.topk``
+    does not promise that order) and their softmax probabilities."""
+    n_cls = logits.shape[1]
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= min(16, n_cls):
+        raise ValueError(f"topk must be an integer in [1, {min(16, n_cls)}], got {k!r}")
+    p = torch.softmax(logits, dim=1)
+    order = torch.sort(logits, dim=1, descending=True, stable=True).indices[:, :int(k)]
+    return order.to(torch.int32), p.gather(1, order)
 
 
 class Done:
@@ -42,14 +77,16 @@ class Done:
 class Executor:
     device = torch.device("cpu")
 
-    def run(self, model: str, images: torch.Tensor | None, start: int, end: int):
+    def run(self, model: str, images: torch.Tensor | None, start: int, end: int, topk: int | None = None):
         raise NotImplementedError
 
-    def submit(self, model: str, images: torch.Tensor | None, start: int, end: int):
+    def submit(self, model: str, images: torch.Tensor | None, start: int, end: int, topk: int | None = None):
         """Start a chunk; ``.result()`` of the returned handle gives what
         ``run`` returns.  Asynchronous executors let the node's worker launch
         chunk k+1 before it post-processes chunk k."""
-        return Done(self.run(model, images, start, end))
+        if topk is None:
+            return Done(self.run(model, images, start, end))
+        return Done(self.run(model, images, start, end, topk=topk))
 
     def warmup(self, model: str, batch: int) -> None:
         pass
@@ -71,9 +108,10 @@ class FakeExecutor(Executor):
 
 
 class TorchExecutor(Executor):
-    def __init__(self, device="cpu", seed: int = 0):
+    def __init__(self, device="cpu", seed: int = 0, weights: dict | None = None):
         self.device = torch.device(device)
         self.seed = seed
+        self.weights = _weights_map(weights)
         self.models: dict[str, torch.nn.Module] = {}
         self.lock = threading.Lock()
 
@@ -82,23 +120,33 @@ class TorchExecutor(Executor):
         with self.lock:
             m = self.models.get(name)
             if m is None:
-                m = ref.build(name, seed=self.seed).to(self.device)
+                if name in self.weights:
+                    from ..models.checkpoint import load_model
+
+                    m = load_model(name, self.weights[name])
+                    _log_digest(name, m, self.weights[name])
+                    m = m.to(self.device)
+                else:
+                    m = ref.build(name, seed=self.seed).to(self.device)
                 self.models[name] = m
         return m
 
     @torch.no_grad()
-    def run(self, model, images, start, end):
+    def run(self, model, images, start, end, topk=None):
         m = self._model(model)
         x = ref.preprocess_u8(images.to(self.device))
+        if topk is not None:
+            cls, prob = stable_topk(m(x).float(), topk)
+            return cls.cpu().numpy(), prob.float().cpu().numpy()
         p = torch.softmax(m(x), dim=1)
         prob, cls = p.max(dim=1)
         return cls.to(torch.int32).cpu().numpy(), prob.float().cpu().numpy()
 
 
 class _HipPending:
-    def __init__(self, ex, slot, ev, out, model=None, images=None):
+    def __init__(self, ex, slot, ev, out, model=None, images=None, topk=None):
         self.ex, self.slot, self.ev, self.out = ex, slot, ev, out
-        self.model, self.images = model, images
+        self.model, self.images, self.topk = model, images, topk
         self._res = None
 
     def result(self):
@@ -106,13 +154,16 @@ class _HipPending:
             try:
                 self.ev.synchronize()
                 out = self.out
-                self._res = (out[:, 0].numpy().copy(), out[:, 1].contiguous().view(torch.float32).numpy().copy())
+                if self.topk is not None:       # (classes [n, k], prob bits [n, k]), each contiguous
+                    self._res = (out[0].numpy().copy(), out[1].view(torch.float32).numpy().copy())
+                else:
+                    self._res = (out[:, 0].numpy().copy(), out[:, 1].contiguous().view(torch.float32).numpy().copy())
             finally:
                 self.ex._release(self.slot)
             if self.images is not None and (self._res[0] < 0).any():
                 # the split range guard tripped (class -2): this chunk again on the
                 # all-f32 kernels, which have fp32's range
-                self._res = self.ex.rerun_exact(self.model, self.images)
+                self._res = self.ex.rerun_exact(self.model, self.images, self.topk)
             self.images = None
         return self._res
 
@@ -128,13 +179,14 @@ class HipExecutor(Executor):
     one critical section (results of two chunks must never mix)."""
 
     def __init__(self, device="cuda", seed: int = 0, use_graphs: bool = True, max_graphs: int = 16,
-                 dtype: str = "fp32", fp32_impl: str = "split"):
+                 dtype: str = "fp32", fp32_impl: str = "split", weights: dict | None = None):
         from .. import ops
         from ..models import HipRunner, build_program
 
         ops.load()  # loud failure if the extension is missing on a GPU host
         self.device = torch.device(device)
         self.seed = seed
+        self.weights = _weights_map(weights)
         self.dtype = dtype
         self.asynchronous = True        # run_packed returns before the GPU finishes
         if fp32_impl not in ("split", "f32mfma"):
@@ -155,6 +207,7 @@ class HipExecutor(Executor):
         # two launch slots (graph set + pinned result buffer each): a chunk can
         # run while the previous one's results are read back and ingested
         self._slots = [None, None]                      # pinned [>= n, 2] int32 per slot
+        self._slots_k = [None, None]                    # top-k: pinned flat int32, >= n * 2k per slot
         self._slot_busy = [False, False]
         self._slot_cv = threading.Condition()
         self._next_slot = 0
@@ -166,7 +219,16 @@ class HipExecutor(Executor):
             r = self.runners.get(name)
             if r is None:
                 with torch.cuda.device(self.device):
-                    r = self._HipRunner(self._build(name, seed=self.seed, dtype=self.dtype), self.device)
+                    if name in self.weights:
+                        from ..models import compile_model
+                        from ..models.checkpoint import load_model
+
+                        m = load_model(name, self.weights[name])
+                        _log_digest(name, m, self.weights[name])
+                        prog = compile_model(m, name, self.dtype)
+                    else:
+                        prog = self._build(name, seed=self.seed, dtype=self.dtype)
+                    r = self._HipRunner(prog, self.device)
                     r.split = self.fp32_impl == "split"
                     # every graph of this executor replays on its one private stream and
                     # its outputs are read (D2H / the caller's packed buffer) before the
@@ -235,18 +297,19 @@ class HipExecutor(Executor):
             self._trim_wanted = False
             torch.cuda.empty_cache()
 
-    def _forward(self, r, images, packed, slot: int = 0):
+    def _forward(self, r, images, packed, slot: int = 0, topk=None):
         """cls, prob of ``images`` on the private stream (caller holds run_lock);
         with ``packed`` the (class, prob bits) pairs are also written there.
-        Launch slot ``slot`` replays its own graph (own static buffers)."""
+        Launch slot ``slot`` replays its own graph (own static buffers); an
+        integer ``topk`` has graphs of its own and returns [n, topk] tensors."""
         n = images.shape[0]
-        if not self.closed and packed is None and (self._can_capture(r) or r.has_graph(n, slot=slot)):
-            got = self._capture(r, lambda: r.capture(n, slot=slot))
+        if not self.closed and packed is None and (self._can_capture(r) or r.has_graph(n, slot=slot, topk=topk)):
+            got = self._capture(r, lambda: r.capture(n, slot=slot, topk=topk))
             if got is not None:
                 sin, replay = got
                 sin.copy_(images)
                 return replay()
-        return r.forward(images.contiguous(), packed=packed)
+        return r.forward(images.contiguous(), packed=packed, topk=topk)
 
     def _enter(self, images):
         if self.stream is None:
@@ -256,11 +319,13 @@ class HipExecutor(Executor):
         images.record_stream(s)
         return s
 
-    def submit(self, model, images, start, end):
+    def submit(self, model, images, start, end, topk=None):
         """Launch one chunk (copy-in, graph replay, pinned D2H) on a free slot
         and return at once; ``.result()`` waits for it and frees the slot.
-        At most two chunks are in flight per executor."""
+        At most two chunks are in flight per executor.  With an integer
+        ``topk`` the result is [n, topk] arrays."""
         r = self.runner(model)
+        topk = r._check_topk(topk)
         n = images.shape[0]
         with self._slot_cv:
             while all(self._slot_busy):
@@ -272,21 +337,33 @@ class HipExecutor(Executor):
             with torch.cuda.device(self.device), self.run_lock:
                 s = self._enter(images)
                 with torch.cuda.stream(s):
-                    cls, prob = self._forward(r, images, None, slot)
-                    host = self._slots[slot]
-                    if host is None or host.shape[0] < n:
-                        host = self._slots[slot] = torch.empty(max(n, 1024), 2, dtype=torch.int32, pin_memory=True)
-                    out = host[:n]
-                    out[:, 0].copy_(cls, non_blocking=True)          # pinned D2H, no pageable bounce
-                    out[:, 1].copy_(prob.view(torch.int32), non_blocking=True)
+                    cls, prob = self._forward(r, images, None, slot, topk)
+                    if topk is not None:
+                        # 2k columns per image: the classes [n, k], then the prob bits [n, k]
+                        need = 2 * n * topk
+                        host = self._slots_k[slot]
+                        if host is None or host.numel() < need:
+                            host = self._slots_k[slot] = torch.empty(max(need, 2 * 1024 * topk), dtype=torch.int32,
+                                                                     pin_memory=True)
+                        out = (host[:n * topk].view(n, topk), host[n * topk:need].view(n, topk))
+                        out[0].copy_(cls, non_blocking=True)
+                        out[1].copy_(prob.view(torch.int32), non_blocking=True)
+                    else:
+                        host = self._slots[slot]
+                        if host is None or host.shape[0] < n:
+                            host = self._slots[slot] = torch.empty(max(n, 1024), 2, dtype=torch.int32,
+                                                                   pin_memory=True)
+                        out = host[:n]
+                        out[:, 0].copy_(cls, non_blocking=True)          # pinned D2H, no pageable bounce
+                        out[:, 1].copy_(prob.view(torch.int32), non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(s)
         except BaseException:
             self._release(slot)
             raise
-        return _HipPending(self, slot, ev, out, model, images)
+        return _HipPending(self, slot, ev, out, model, images, topk)
 
-    def rerun_exact(self, model, images):
+    def rerun_exact(self, model, images, topk=None):
         """(cls, prob) of ``images`` on the all-f32-MFMA kernels: the fallback
         for a chunk whose split forward left fp16's range."""
         r = self.runner(model)
@@ -294,7 +371,7 @@ class HipExecutor(Executor):
             s = self._enter(images)
             with torch.cuda.stream(s):
                 z = r.logits_f32_exact(images.contiguous())
-                cls, prob = r.ops.softmax_top1(z)
+                cls, prob = r.ops.softmax_top1(z) if topk is None else r.ops.softmax_topk(z, topk)
                 res = (cls.cpu().numpy().astype(np.int32), prob.cpu().numpy().astype(np.float32))
         return res
 
@@ -303,8 +380,8 @@ class HipExecutor(Executor):
             self._slot_busy[slot] = False
             self._slot_cv.notify_all()
 
-    def run(self, model, images, start, end):
-        return self.submit(model, images, start, end).result()
+    def run(self, model, images, start, end, topk=None):
+        return self.submit(model, images, start, end, topk).result()
 
     def run_packed(self, model, images, packed):
         """Device-resident result path (collective rounds): write (class, prob
@@ -372,14 +449,15 @@ class HipExecutor(Executor):
             r.close()
 
 
-def make_executor(kind: str, device=None, seed: int = 0, dtype: str = "fp32", fp32_impl: str = "split") -> Executor:
+def make_executor(kind: str, device=None, seed: int = 0, dtype: str = "fp32", fp32_impl: str = "split",
+                  weights: dict | None = None) -> Executor:
     kind = kind.lower()
     if kind == "auto":
         kind = "hip" if torch.cuda.is_available() else "torch"
     if kind == "hip":
-        return HipExecutor(device or "cuda", seed=seed, dtype=dtype, fp32_impl=fp32_impl)
+        return HipExecutor(device or "cuda", seed=seed, dtype=dtype, fp32_impl=fp32_impl, weights=weights)
     if kind == "torch":
-        return TorchExecutor(device or "cpu", seed=seed)
+        return TorchExecutor(device or "cpu", seed=seed, weights=weights)
     if kind == "fake":
         return FakeExecutor()
     raise ValueError(f"unknown executor {kind!r}")
