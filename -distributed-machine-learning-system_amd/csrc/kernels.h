@@ -262,7 +262,8 @@ struct alignas(16) JpegImageDesc {
   int pitch[3];              // plane pitch: 8 * bw rounded up to 16 (a lane stores two blocks' rows at once)
   int cw[3], ch[3];          // the plane's valid (downsampled) size: ceil(W h / hmax) x ceil(H v / vmax)
   int W, H, ncomp;
-  int mode;                  // chroma: 0 full size, 1 half width (h2v1), 2 half width and height (h2v2)
+  int mode;                  // chroma: 0 full size, 1 half width (h2v1), 2 half width and height (h2v2),
+                             // 3 half height (h1v2, 4:4:0), 4 quarter width (h4v1, 4:1:1)
   int rw, rh;                // size after the resize (W, H: no resize)
   int left, top;             // crop origin in the resized image
   int out_w, out_h;
@@ -276,6 +277,10 @@ struct JpegSeg {
 // coefficients -> uint8 component planes; nslots = 2 * (pairs of all nseg segments) block slots
 void jpeg_idct_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs, int nseg,
                       int nslots, hipStream_t st);
+// the same launch shape after jpeg_idct_launch: rewrites the planes of the images of mode 3 / 4 from an fp64
+// IDCT (ties round as the float64 model's); the slots of every other image are left as they are
+void jpeg_idct_exact_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs,
+                            int nseg, int nslots, hipStream_t st);
 // planes -> RGB, resized and cropped: nimg images of at most max_pix output pixels each
 void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,
                              hipStream_t st);

@@ -12,8 +12,14 @@
 //                              row y of two horizontally adjacent blocks side by
 //                              side: the pair's even lane stores 16 bytes (plane
 //                              pitch rounded up to 16).
+//   * jpeg_idct_exact_kernel   the planes of mode-3 / mode-4 images (4:4:0, 4:1:1) again
+//                              in fp64 over the former's output, so that their
+//                              samples round as the float64 model's; launched only
+//                              for a batch that holds such an image.
 //   * jpeg_resize_crop_kernel  one thread per output pixel: chroma "fancy"
-//                              upsampling (libjpeg's integer triangle filters),
+//                              upsampling (libjpeg's integer triangle filters for
+//                              h2v1, h2v2 and h1v2; replication for h4v1, as
+//                              libjpeg has no filter for that ratio),
 //                              YCbCr -> RGB rounded to uint8, Pillow's BILINEAR
 //                              horizontal pass rounded to uint8, vertical pass
 //                              rounded to uint8, centre crop.  rw == W / rh == H
@@ -125,6 +131,75 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
 
 namespace {
 
+// the type-III DCT matrix [sample][frequency] in fp64: 0.5 cos((2x + 1) u pi / 16), column 0 times sqrt(1/2)
+__constant__ double kIdctD[64] = {
+    0.3535533905932738, 0.4903926402016152, 0.46193976625564337, 0.4157348061512726, 0.3535533905932738, 0.27778511650980114, 0.19134171618254492, 0.09754516100806417,
+    0.3535533905932738, 0.4157348061512726, 0.19134171618254492, -0.0975451610080641, -0.35355339059327373, -0.4903926402016152, -0.4619397662556434, -0.2777851165098011,
+    0.3535533905932738, 0.27778511650980114, -0.19134171618254486, -0.4903926402016152, -0.35355339059327384, 0.09754516100806415, 0.46193976625564326, 0.41573480615127273,
+    0.3535533905932738, 0.09754516100806417, -0.46193976625564337, -0.2777851165098011, 0.3535533905932737, 0.41573480615127273, -0.19134171618254495, -0.4903926402016153,
+    0.3535533905932738, -0.0975451610080641, -0.4619397662556434, 0.2777851165098009, 0.35355339059327384, -0.41573480615127256, -0.19134171618254528, 0.4903926402016152,
+    0.3535533905932738, -0.277785116509801, -0.19134171618254517, 0.4903926402016152, -0.35355339059327334, -0.09754516100806401, 0.46193976625564337, -0.4157348061512725,
+    0.3535533905932738, -0.4157348061512727, 0.191341716182545, 0.09754516100806439, -0.35355339059327356, 0.4903926402016153, -0.4619397662556432, 0.27778511650980076,
+    0.3535533905932738, -0.4903926402016152, 0.46193976625564326, -0.41573480615127256, 0.3535533905932733, -0.27778511650980076, 0.19134171618254478, -0.09754516100806429};
+
+}  // namespace
+
+// The planes of the images of mode 3 and 4 once more, in fp64, over jpeg_idct_kernel's output (same slots,
+// launched after it when the batch holds such an image; every other image's slots return at once).  Their
+// colour stage hands a chroma sample on undiluted (mode 4 replicates it, mode 3 filters along one axis
+// only), and R = Y + 1.402 Cr, B = Y + 1.772 Cb turn one level of chroma into two of colour, so a sample
+// whose exact value lies within fp32's reach of a rounding tie (164.5000034 was met) must round as the
+// float64 model rounds it.  Lane (b, x): column x of block b; row pass over the 64 dequantised coefficients
+// (exact integers in fp64), column pass, + 128, round half up, clamp, one byte per row.
+__global__ __launch_bounds__(256) void jpeg_idct_exact_kernel(const int16_t* __restrict__ coef,
+                                                              uint8_t* __restrict__ planes,
+                                                              const JpegImageDesc* __restrict__ desc,
+                                                              const JpegSeg* __restrict__ segs, int nseg, int nslots) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = lane >> 3, x = lane & 7;
+  const int slot = (blockIdx.x * 4 + wave) * 8 + b;           // jpeg_idct_kernel's numbering
+  if (slot >= nslots) return;
+  const int pair = slot >> 1;
+  const JpegSeg sg = segs[find_seg(segs, nseg, pair)];
+  const JpegImageDesc& d = desc[sg.img];
+  if (d.ncomp != 3 || d.mode < 3) return;
+  const int comp = sg.comp;
+  const int bw = d.bw[comp], bwp = (bw + 1) >> 1;
+  const int lp = pair - sg.pair_start;
+  const int by = lp / bwp;
+  const int bx = 2 * (lp - by * bwp) + (slot & 1);
+  if (bx >= bw) return;                                       // the block past an odd row's end: padding
+  const int16_t* cb = coef + ((size_t)d.blk_off[comp] + (size_t)by * bw + bx) * 64;
+  double mx[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) mx[u] = kIdctD[x * 8 + u];
+  double s[8];                                                // s[v] = sum_u M(x, u) F[v][u]
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const vec16 cv = *reinterpret_cast<const vec16*>(cb + v * 8);
+    const vec16 qv = *reinterpret_cast<const vec16*>(&d.q[comp][v * 8]);
+    const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+    double a = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      a = fma(mx[2 * i], (double)((int)(int16_t)(cw[i] & 0xFFFFu) * (int)(qw[i] & 0xFFFFu)), a);
+      a = fma(mx[2 * i + 1], (double)((int)(int16_t)(cw[i] >> 16) * (int)(qw[i] >> 16)), a);
+    }
+    s[v] = a;
+  }
+  // bx * 8 + x < 8 * bw <= pitch, by * 8 + y < 8 * bh: inside the plane jpeg_plan laid out
+  uint8_t* dst = planes + d.plane_off[comp] + (size_t)(by * 8) * (size_t)d.pitch[comp] + bx * 8 + x;
+#pragma unroll
+  for (int y = 0; y < 8; ++y) {
+    double a = 128.5;                                         // + 128, round half up by the floor below
+#pragma unroll
+    for (int v = 0; v < 8; ++v) a = fma(kIdctD[y * 8 + v], s[v], a);
+    dst[(size_t)y * (size_t)d.pitch[comp]] = (uint8_t)fmin(fmax(floor(a), 0.0), 255.0);
+  }
+}
+
+namespace {
+
 struct Planes {
   const uint8_t* y;
   const uint8_t* cb;
@@ -138,6 +213,12 @@ struct Planes {
 __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int pitch, int cw, int ch, int mode, int x,
                                          int y) {
   if (mode == 0) return p[(size_t)y * pitch + x];
+  if (mode == 3) {                                   // h1v2: libjpeg's vertical triangle filter, columns as they are
+    const int j = y >> 1;
+    const int jf = (y & 1) ? min(j + 1, ch - 1) : max(j - 1, 0);
+    return (3 * p[(size_t)j * pitch + x] + p[(size_t)jf * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
+  }
+  if (mode == 4) return p[(size_t)y * pitch + (x >> 2)];   // h4v1: replication, libjpeg has no filter for 4:1
   const int i = x >> 1;
   if (mode == 1) {
     const uint8_t* row = p + (size_t)y * pitch;
@@ -273,6 +354,13 @@ void jpeg_idct_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc*
   if (nslots <= 0) return;
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nslots + 31) / 32)), dim3(256), 0, st, coef, planes, desc,
                      segs, nseg, nslots);
+}
+
+void jpeg_idct_exact_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs,
+                            int nseg, int nslots, hipStream_t st) {
+  if (nslots <= 0) return;
+  hipLaunchKernelGGL(jpeg_idct_exact_kernel, dim3((unsigned)((nslots + 31) / 32)), dim3(256), 0, st, coef, planes,
+                     desc, segs, nseg, nslots);
 }
 
 void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,

@@ -8,6 +8,10 @@
 // With native_progressive the parser also walks a progressive file's scans up
 // to EOI into a scan script, and jpeg_decode runs the shared scan core of
 // ../jpeg_huff_prog.h over it; baseline files take the same path as without it.
+//
+// With native_sampling the parser also accepts the 4:4:0 (luma 1x2) and 4:1:1
+// (luma 4x1) layouts as modes 3 and 4; the decode loops are the same, they take
+// every h, v in 1..4 from the header.
 #include "jpeg_entropy.h"
 
 #include <algorithm>
@@ -125,8 +129,9 @@ int script_tab(const RawTabs& raw, int slot, JpegProgScript* script) {
 }
 
 // native: an SOF2 frame is walked to EOI (script, when given, receives its scans)
+// sampling: luma 1x2 and 4x1 over 1x1 chroma are modes 3 and 4, not JPEG_UNSUPPORTED_SAMPLING
 int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, bool native = false,
-          JpegProgScript* script = nullptr) {
+          JpegProgScript* script = nullptr, bool sampling = false) {
   if (data == nullptr || n == 0) return JPEG_EMPTY;
   if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_NOT_JPEG;
   std::memset(hdr, 0, sizeof(*hdr));
@@ -183,6 +188,8 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           if (cp[0].h == cp[1].h && cp[0].v == cp[1].v) hdr->mode = 0;
           else if (cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 2 && cp[0].v == 1) hdr->mode = 1;
           else if (cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 2 && cp[0].v == 2) hdr->mode = 2;
+          else if (sampling && cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 1 && cp[0].v == 2) hdr->mode = 3;
+          else if (sampling && cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 4 && cp[0].v == 1) hdr->mode = 4;
           else return JPEG_UNSUPPORTED_SAMPLING;
         }
         hdr->hmax = hdr->comp[0].h;
@@ -441,10 +448,11 @@ const char* jpeg_status_name(int status) {
   return status >= 0 && status < JPEG_STATUS_COUNT ? names[status] : "unknown";
 }
 
-int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive, JpegProgScript* script) {
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive, JpegProgScript* script,
+                      bool native_sampling) {
   std::vector<Tables> tb(1);                             // ~9 KB: off the stack
   Scan sc;
-  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script);
+  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script, native_sampling);
 }
 
 void jpeg_prog_frame_desc(const JpegHeader& h, JpegHuffDesc* d) {
@@ -486,12 +494,13 @@ int decode_progressive(const uint8_t* data, size_t n, const JpegHeader& hdr, con
 
 }  // namespace
 
-int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, bool native_progressive) {
+int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, bool native_progressive,
+                bool native_sampling) {
   std::vector<Tables> tbv(1);
   Tables& tb = tbv[0];
   Scan sc;
   JpegProgScript script;
-  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr);
+  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr, native_sampling);
   if (st != JPEG_OK) return st;
   if (out == nullptr || (size_t)hdr->total_coefs > out_cap) return JPEG_BUFFER_TOO_SMALL;
   std::memset(out, 0, (size_t)hdr->total_coefs * sizeof(int16_t));
@@ -530,13 +539,14 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
 
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
                        int16_t* const* out, const size_t* out_cap, int* status, int nthreads,
-                       bool native_progressive) {
+                       bool native_progressive, bool native_sampling) {
   std::atomic<int> next{0};
   auto work = [&]() {
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) return;
-      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive);
+      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY
+                                     : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive, native_sampling);
     }
   };
   const int nt = std::max(1, std::min(nthreads, n));

@@ -10,7 +10,8 @@
 // each other at JpegComp::coef_off (in int16 elements).
 //
 // Progressive files (SOF2) are refused unless a caller passes native_progressive;
-// then they decode into the same layout (../jpeg_huff_prog.h).
+// then they decode into the same layout (../jpeg_huff_prog.h).  The 4:4:0 and
+// 4:1:1 chroma layouts are refused unless a caller passes native_sampling.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -31,7 +32,7 @@ enum JpegStatus : int {
   JPEG_UNSUPPORTED_PRECISION = 6,   // 12-bit samples
   JPEG_UNSUPPORTED_COMPONENTS = 7,  // 4 components (CMYK / YCCK), or 2
   JPEG_UNSUPPORTED_QUANT16 = 8,     // 16-bit quantisation tables
-  JPEG_UNSUPPORTED_SAMPLING = 9,    // not 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2)
+  JPEG_UNSUPPORTED_SAMPLING = 9,    // not 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2); with native_sampling: nor 4:4:0 (1x2) / 4:1:1 (4x1)
   JPEG_UNSUPPORTED_SIZE = 10,       // above 4096 x 4096
   JPEG_UNSUPPORTED_MULTISCAN = 11,  // baseline with one scan per component; progressive above kJpegProgMaxScans
   JPEG_UNSUPPORTED_SOF = 12,        // lossless / hierarchical frames
@@ -55,7 +56,8 @@ struct JpegHeader {
   int W, H;
   int ncomp;           // 1 or 3
   int hmax, vmax;
-  int mode;            // chroma layout: 0 as luma, 1 half width (h2v1), 2 half width and height (h2v2)
+  int mode;            // chroma layout: 0 as luma, 1 half width (h2v1), 2 half width and height (h2v2);
+                       // with native_sampling also 3 half height (h1v2, 4:4:0), 4 quarter width (h4v1, 4:1:1)
   int mcux, mcuy;      // MCU grid
   int restart_interval;
   uint32_t total_coefs;   // int16 elements the coefficient buffer must hold
@@ -83,8 +85,11 @@ struct JpegProgScript {
 // a scan that uses an undefined table and a file without EOI; more than
 // kJpegProgMaxScans scans are JPEG_UNSUPPORTED_MULTISCAN.  A component's
 // quantisation table is the one in its slot at that component's first scan.
+// native_sampling: a 3-component frame whose chroma components are both 1x1 and
+// whose luma is 1x2 or 4x1 is accepted as mode 3 or 4; every other layout beyond
+// modes 0..2 stays JPEG_UNSUPPORTED_SAMPLING.
 int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive = false,
-                      JpegProgScript* script = nullptr);
+                      JpegProgScript* script = nullptr, bool native_sampling = false);
 
 // The frame layout of *hdr in a JpegHuffDesc (ncomp, MCU grid, per component
 // sampling, padded grid, own grid, coefficient offsets, total_coefs): what
@@ -95,15 +100,15 @@ void jpeg_prog_frame_desc(const JpegHeader& hdr, JpegHuffDesc* d);
 // reads outside data[0, n) nor writes outside out[0, out_cap).
 // native_progressive: a progressive file is decoded with the core of
 // jpeg_huff_prog.h on a word-aligned copy of its scans; baseline files are
-// decoded as without it.
+// decoded as without it.  native_sampling: as for jpeg_parse_header.
 int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap,
-                bool native_progressive = false);
+                bool native_progressive = false, bool native_sampling = false);
 
 // Decodes n images on a pool of `nthreads` std::threads (never derived from
 // the machine's CPU count).  Image i with data[i] == nullptr is skipped with
 // JPEG_EMPTY.  status[i] and hdr[i] are written for every i.
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
                        int16_t* const* out, const size_t* out_cap, int* status, int nthreads = 8,
-                       bool native_progressive = false);
+                       bool native_progressive = false, bool native_sampling = false);
 
 }  // namespace idunno

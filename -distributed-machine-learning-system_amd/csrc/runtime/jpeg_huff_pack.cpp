@@ -141,7 +141,8 @@ size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 }  // namespace
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive, bool restart_intervals) {
+                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive, bool restart_intervals,
+                    bool native_sampling) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
   out->scans.clear();
@@ -162,7 +163,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       status[i] = JPEG_EMPTY;
       continue;
     }
-    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script);
+    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script, native_sampling);
     if (status[i] != JPEG_OK) continue;
     const JpegHeader& h = hdr[i];
     if (h.progressive) {
@@ -312,7 +313,8 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 namespace {
 
 const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
-                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog, bool allow_rst) {
+                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog, bool allow_rst,
+                      bool allow_sampling) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
   int64_t scratch_at = 0;
   if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
@@ -341,6 +343,9 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
       co += (int64_t)d.bw[c] * d.bh[c] * 64;
     }
     if (co != (int64_t)d.total_coefs) return "coefficient count";
+    if (!allow_sampling && d.ncomp == 3 && d.h[1] == 1 && d.v[1] == 1 && d.h[2] == 1 && d.v[2] == 1 &&
+        ((d.h[0] == 1 && d.v[0] == 2) || (d.h[0] == 4 && d.v[0] == 1)))
+      return "sampling layout of a batch planned without native_sampling";
     if (d.gpu == 4 && d.restart_interval < 1) return "restart interval";
     if (d.gpu == 2) {
       const JpegParDesc& p = par[i];
@@ -360,15 +365,15 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
 }  // namespace
 
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog, bool allow_rst) {
-  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst);
+                            bool allow_prog, bool allow_rst, bool allow_sampling) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst, allow_sampling);
 }
 
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog, bool allow_rst) {
+                                bool allow_prog, bool allow_rst, bool allow_sampling) {
   if (par == nullptr) return "no sub-stream descriptors";
-  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst);
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst, allow_sampling);
 }
 
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,

@@ -35,7 +35,7 @@ from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
-# (device, directory, entropy_on, progressive, restart) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# (device, directory, entropy_on, progressive, restart, sampling) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
 # index only; after replacing files of a directory call drop_gpu_sources()
 _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
@@ -66,7 +66,7 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
                  data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host",
                  progressive: str = "fallback", restart: str = "lane", topk: int = 1, weights=None,
-                 classes: str | None = None):
+                 classes: str | None = None, sampling: str = "fallback"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
     ``topk`` > 1 (at most 16) returns ``(image_name, (cat_1..cat_k),
@@ -88,7 +88,10 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     form instead of handing them to Pillow; the default is ``"fallback"``.
     ``restart="intervals"`` (with ``decoder="gpu"`` and a device
     ``entropy_on``) decodes baseline files with a restart interval one interval
-    per lane instead of on one lane; the default is ``"lane"``."""
+    per lane instead of on one lane; the default is ``"lane"``.
+    ``sampling="native"`` (with ``decoder="gpu"``) decodes 4:4:0 and 4:1:1
+    JPEG files natively instead of handing them to Pillow; the default is
+    ``"fallback"``."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
     if entropy_on not in ("host", "gpu", "gpu_parallel"):
@@ -97,6 +100,8 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         raise ValueError(f"progressive must be 'fallback' or 'native', not {progressive!r}")
     if restart not in ("lane", "intervals"):
         raise ValueError(f"restart must be 'lane' or 'intervals', not {restart!r}")
+    if sampling not in ("fallback", "native"):
+        raise ValueError(f"sampling must be 'fallback' or 'native', not {sampling!r}")
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 16:
         raise ValueError(f"topk must be an integer in [1, 16], not {topk!r}")
     t0 = time.time()
@@ -110,11 +115,11 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         src = SyntheticSource(data_seed, device)
     elif decoder == "gpu":
         with _LOCK:
-            key = (str(device), os.path.abspath(d), entropy_on, progressive, restart)
+            key = (str(device), os.path.abspath(d), entropy_on, progressive, restart, sampling)
             src = _GPU_SOURCES.get(key)
             if src is None:
                 src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on, progressive=progressive,
-                                                              restart=restart)
+                                                              restart=restart, sampling=sampling)
     else:
         src = JpegSource(device, root=d)
     names = class_names(path=classes)
@@ -151,6 +156,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--restart", default="lane", choices=["lane", "intervals"],
                     help="with --decoder gpu and a device --entropy: a file with restart markers on one lane, or one "
                          "restart interval per lane")
+    ap.add_argument("--sampling", default="fallback", choices=["fallback", "native"],
+                    help="with --decoder gpu: 4:4:0 and 4:1:1 JPEG files through Pillow, or decoded natively")
     ap.add_argument("--topk", type=int, default=1, help="categories per image, most probable first (1..16)")
     ap.add_argument("--weights", default=None,
                     help="checkpoint file for the model (.safetensors or a torch.save'd state dict); default random-init")
@@ -162,7 +169,7 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
                            decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive, restart=a.restart,
-                           topk=a.topk, weights=a.weights, classes=a.classes)
+                           topk=a.topk, weights=a.weights, classes=a.classes, sampling=a.sampling)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

@@ -78,7 +78,8 @@ def run_node(a) -> int:
     if a.source == "jpeg":
         # real files: `put` test_<i>.JPEG into SDFS, then `inference <start> <end> <model>`
         node.source = GpuJpegSource(sdfs=node.sdfs, device=dev, entropy_on=a.jpeg_entropy,
-                                    progressive=a.jpeg_progressive, restart=a.jpeg_restart)
+                                    progressive=a.jpeg_progressive, restart=a.jpeg_restart,
+                                    sampling=a.jpeg_sampling)
     else:
         node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
                        else SyntheticSource(cfg.data_seed, dev))
@@ -104,7 +105,7 @@ def run_cluster(a) -> int:
     procs = []
     base = [sys.executable, "-m", "idunno.launch", "node", "--executor", a.executor, "--source", a.source,
             "--jpeg-entropy", a.jpeg_entropy, "--jpeg-progressive", a.jpeg_progressive,
-            "--jpeg-restart", a.jpeg_restart]
+            "--jpeg-restart", a.jpeg_restart, "--jpeg-sampling", a.jpeg_sampling]
     for flag, v in (("--config", a.config), ("--nodes", cfg.num_nodes), ("--base-port", cfg.base_port),
                     ("--store-root", cfg.store_root), ("--log-dir", a.log_dir)):
         if v is not None:
@@ -159,6 +160,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--jpeg-restart", default="lane", choices=["lane", "intervals"],
                     help="--source jpeg with a device --jpeg-entropy: a file with restart markers on one lane, or one "
                          "restart interval per lane")
+    ap.add_argument("--jpeg-sampling", default="fallback", choices=["fallback", "native"],
+                    help="--source jpeg: 4:4:0 and 4:1:1 files through Pillow, or decoded natively")
     ap.add_argument("--weights", action="append", default=None, metavar="MODEL=PATH",
                     help="checkpoint file for a model (repeatable); every node reads the same file")
     ap.add_argument("--shell", action="store_true")

@@ -353,24 +353,25 @@ def synth_images(seed: int, start: int, n: int, device, hw: int = 224):
 
 # ---- JPEG decode (runtime/jpeg.py drives these) ---------------------------------------
 
-def jpeg_parse(data: bytes, native_progressive: bool = False):
+def jpeg_parse(data: bytes, native_progressive: bool = False, native_sampling: bool = False):
     """Markers of a JPEG up to SOS: (status, reason, header dict or None);
     status 0 = a baseline file the native decoder takes.  With
-    ``native_progressive`` a progressive file is walked up to EOI and taken too."""
-    return load().jpeg_parse(data, bool(native_progressive))
+    ``native_progressive`` a progressive file is walked up to EOI and taken too;
+    with ``native_sampling`` a 4:4:0 or 4:1:1 frame is taken as ``mode`` 3 or 4."""
+    return load().jpeg_parse(data, bool(native_progressive), bool(native_sampling))
 
 
-def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False):
+def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False, native_sampling: bool = False):
     """Huffman-decode a list of ``bytes | None`` on ``threads`` native threads
     (GIL released): (status per entry, headers, int16 coefficients on the
     host, first coefficient of each entry or -1)."""
-    return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive))
+    return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive), bool(native_sampling))
 
 
 # the sub-stream kernel's constants, then the progressive decoder's: the scan cap of one file
-# (csrc/jpeg_huff_prog.h) and where a header row keeps its ``progressive`` int
+# (csrc/jpeg_huff_prog.h) and where a header row keeps its ``progressive`` and ``mode`` ints
 _JPEG_PAR_CONSTANTS = ("JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS", "JPEG_PROG_MAX_SCANS",
-                       "JPEG_HEADER_PROGRESSIVE_OFFSET")
+                       "JPEG_HEADER_PROGRESSIVE_OFFSET", "JPEG_HEADER_MODE_OFFSET")
 
 
 def __getattr__(name: str):
@@ -382,7 +383,7 @@ def __getattr__(name: str):
 
 
 def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = False,
-                   restart_intervals: bool = False):
+                   restart_intervals: bool = False, native_sampling: bool = False):
     """Parse a list of ``bytes | None`` and pack the accepted entries for the
     device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
     ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
@@ -394,8 +395,11 @@ def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = Fal
     ``RSTn`` markers the packer finds (``n_rst`` entries) get one work item per
     interval in ``rst_items`` (int32 ``[items, 4]``: entry, first byte, first
     MCU, interval index) for the interval kernel, which the same two calls
-    launch; ``n_lane`` keeps counting the entries of the one-lane kernel."""
-    return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive), bool(restart_intervals))
+    launch; ``n_lane`` keeps counting the entries of the one-lane kernel.
+    ``native_sampling``: 4:4:0 and 4:1:1 files are accepted (modes 3 and 4 in
+    their header rows) and packed like every other file of their kind."""
+    return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive), bool(restart_intervals),
+                                 bool(native_sampling))
 
 
 def jpeg_entropy_zero(coefs):

@@ -37,11 +37,20 @@ is decoded by the serial decoder's own loop from the serial decoder's own
 state.  With ``"lane"`` such a file is walked by one lane of the one-lane
 kernel, whatever the form.
 
+``sampling="native"`` (opt-in, default ``"fallback"``) takes two more chroma
+layouts in all three forms: 4:4:0 (luma 1x2, what a 4:2:2 file becomes after
+a lossless 90 degree rotation) as ``mode`` 3 and 4:1:1 (luma 4x1) as ``mode``
+4.  The entropy cores take any sampling factors from the header; the colour
+stage upsamples mode 3 with libjpeg's vertical triangle filter and mode 4 by
+replication, as libjpeg-turbo does, on planes that an fp64 IDCT pass
+(jpeg_idct_exact_kernel) has rewritten so that near-ties round as the model's.
+
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
 crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
 decoder does not take (progressive unless ``progressive="native"``,
-non-interleaved baseline, arithmetic, 12-bit, CMYK, odd sampling,
+non-interleaved baseline, arithmetic, 12-bit, CMYK, 4:4:0 / 4:1:1 unless
+``sampling="native"``, any other odd sampling,
 corrupt, not a JPEG at all) are decoded by ``load_image_u8`` on the host and
 reported in ``info["fallbacks"]``; on a CPU device every image takes that
 path.  ``reference_backend`` is the float64 numpy model of the GPU chain.
@@ -83,26 +92,38 @@ def _check_restart(restart: str) -> str:
     return restart
 
 
-def parse(data: bytes, progressive: str = "fallback"):
+SAMPLING = ("fallback", "native")
+
+
+def _check_sampling(sampling: str) -> str:
+    if sampling not in SAMPLING:
+        raise ValueError(f"sampling must be one of {SAMPLING}, not {sampling!r}")
+    return sampling
+
+
+def parse(data: bytes, progressive: str = "fallback", sampling: str = "fallback"):
     """Header of a JPEG the native decoder takes (dict: W, H, ncomp, mode,
     comp[i] = h, v, bw, bh, coef_off, q, progressive, nscans), or the reason
     (str) it does not.  A progressive file is ``"progressive"`` unless
-    ``progressive="native"``."""
+    ``progressive="native"``; a 4:4:0 or 4:1:1 file is ``"sampling"`` unless
+    ``sampling="native"`` (then ``mode`` 3 or 4)."""
     native = _check_progressive(progressive) == "native"
-    st, reason, hdr = _C().jpeg_parse(bytes(data), native)
+    samp = _check_sampling(sampling) == "native"
+    st, reason, hdr = _C().jpeg_parse(bytes(data), native, samp)
     return hdr if st == 0 else reason
 
 
-def entropy_decode(data: bytes, progressive: str = "fallback"):
+def entropy_decode(data: bytes, progressive: str = "fallback", sampling: str = "fallback"):
     """(header, int16 coefficients) of one image by the native host decoder, or
     the reason (str) it was refused."""
     native = _check_progressive(progressive) == "native"
+    samp = _check_sampling(sampling) == "native"
     data = bytes(data)
-    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native)
+    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native, samp)
     if status[0] != 0:
-        st, reason, _ = _C().jpeg_parse(data, native)
+        st, reason, _ = _C().jpeg_parse(data, native, samp)
         return reason if st != 0 else "corrupt"
-    return parse(data, progressive), coefs.numpy()
+    return parse(data, progressive, sampling), coefs.numpy()
 
 
 # ---- float64 model of the GPU chain ------------------------------------------------
@@ -148,10 +169,21 @@ def _upsample_h2v2(p: np.ndarray) -> np.ndarray:
     return out
 
 
+def _upsample_h1v2(p: np.ndarray) -> np.ndarray:
+    p = p.astype(np.int32)
+    above = np.concatenate([p[:1], p[:-1]], 0)
+    below = np.concatenate([p[1:], p[-1:]], 0)
+    out = np.empty((2 * p.shape[0], p.shape[1]), np.int32)
+    out[0::2] = (3 * p + above + 1) >> 2
+    out[1::2] = (3 * p + below + 2) >> 2
+    return out
+
+
 def reference_backend(header: dict, coeffs: np.ndarray) -> np.ndarray:
     """Full-resolution RGB uint8 [H, W, 3] from a header and its coefficients:
     exact IDCT in float64, planes cut to their downsampled size, libjpeg's
-    fancy upsampling, colour conversion rounded half up."""
+    fancy upsampling (mode 4, h4v1: replication, libjpeg has no filter for
+    it), colour conversion rounded half up."""
     W, H = header["W"], header["H"]
     hmax, vmax = header["hmax"], header["vmax"]
     m = _idct_matrix()
@@ -166,7 +198,8 @@ def reference_backend(header: dict, coeffs: np.ndarray) -> np.ndarray:
     y = planes[0]
     if len(planes) == 1:
         return np.repeat(y[:, :, None], 3, 2).astype(np.uint8)
-    up = {0: lambda p: p, 1: _upsample_h2v1, 2: _upsample_h2v2}[header["mode"]]
+    up = {0: lambda p: p, 1: _upsample_h2v1, 2: _upsample_h2v2, 3: _upsample_h1v2,
+          4: lambda p: np.repeat(p, 4, 1)}[header["mode"]]
     cb = up(planes[1])[:H, :W].astype(np.float64) - 128.0
     cr = up(planes[2])[:H, :W].astype(np.float64) - 128.0
     rgb = np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], 2)
@@ -234,10 +267,10 @@ _DEVICE_FORMS = ("gpu", "gpu_parallel")
 _UNSYNCED = 100           # kJpegHuffUnsynced: the sub-stream kernel's rounds hit their cap (device-only status)
 
 
-def _refusal(C, data: bytes, status: int, native: bool = False) -> str:
-    """Why an entry is a fallback: the parse's reason (in the progressive mode the batch
-    was decoded in), else what the entropy stage said."""
-    st, reason, _ = C.jpeg_parse(data, native)
+def _refusal(C, data: bytes, status: int, native: bool = False, samp: bool = False) -> str:
+    """Why an entry is a fallback: the parse's reason (in the progressive and sampling modes
+    the batch was decoded in), else what the entropy stage said."""
+    st, reason, _ = C.jpeg_parse(data, native, samp)
     if st != 0:
         return reason
     return "unsynced" if status == _UNSYNCED else "corrupt"
@@ -250,7 +283,7 @@ def _check_entropy_on(entropy_on: str) -> str:
 
 
 def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback",
-                  restart: str = "lane"):
+                  restart: str = "lane", sampling: str = "fallback"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
@@ -259,18 +292,20 @@ def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive
     thread, GIL released as well).  ``progressive="native"`` takes progressive
     files in either form; ``restart="intervals"`` packs one work item per
     restart interval for the interval kernel in the two device forms (the host
-    form is unchanged by it).  Returns what ``decode_batch(..., entropy=)``
-    takes; the result remembers the options."""
+    form is unchanged by it); ``sampling="native"`` takes 4:4:0 and 4:1:1 files
+    in every form.  Returns what ``decode_batch(..., entropy=)`` takes; the
+    result remembers the options."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
     intervals = _check_restart(restart) == "intervals"
+    samp = _check_sampling(sampling) == "native"
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
     if entropy_on in _DEVICE_FORMS:
-        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals)
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp)
         return entropy_on, datas, packed, time.perf_counter() - t0
-    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native)
-    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive
+    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native, samp)
+    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive, sampling
 
 
 def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
@@ -305,28 +340,30 @@ def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
 
 
 def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8, progressive: str = "fallback",
-                  restart: str = "lane"):
+                  restart: str = "lane", sampling: str = "fallback"):
     """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
     from the host decoder or, with ``entropy_on="gpu"`` / ``"gpu_parallel"`` on a
     GPU ``device``, from the entropy kernels.  ``progressive="native"``:
     progressive files are decoded too, in every form.  ``restart="intervals"``:
-    the device forms decode restart-interval files one interval per lane."""
+    the device forms decode restart-interval files one interval per lane.
+    ``sampling="native"``: 4:4:0 and 4:1:1 files are decoded too, in every form."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
     intervals = _check_restart(restart) == "intervals"
+    samp = _check_sampling(sampling) == "native"
     C = _C()
     datas = [None if d is None else bytes(d) for d in datas]
     if entropy_on == "host":
-        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native)
+        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native, samp)
         return list(status), list(offs), coefs
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals)
+    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp)
     status = list(packed.status)
     coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
     if packed.n_gpu:
@@ -343,7 +380,7 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
 
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
                  stager: HbmStager | None = None, entropy=None, entropy_on: str = "host",
-                 progressive: str = "fallback", restart: str = "lane"):
+                 progressive: str = "fallback", restart: str = "lane", sampling: str = "fallback"):
     """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
     ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
     resized or cropped and the result is a list of [H, W, 3] tensors (``None``
@@ -399,10 +436,24 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     in a device form, the one it was prepared in; on a CPU device and in the
     host form the one asked for, and nothing changes there),
     ``info["restart_images"]`` counts the images the interval kernel decoded
-    and did not flag."""
+    and did not flag.
+
+    ``sampling="native"`` (default ``"fallback"``: a 4:4:0 or 4:1:1 file goes
+    to ``load_image_u8`` with the reason ``"sampling"``) decodes 3-component
+    files whose chroma components are 1x1 and whose luma is 1x2 (4:4:0, header
+    ``mode`` 3) or 4x1 (4:1:1, ``mode`` 4) natively in every ``entropy_on``
+    form, baseline, restart-interval and progressive alike: the entropy cores
+    take the factors from the header, the resize kernel upsamples mode 3 with
+    libjpeg's vertical triangle filter and mode 4 by replication.  Every other
+    layout stays a ``"sampling"`` fallback.  ``info["sampling"]`` names the
+    mode in effect (when ``entropy`` was prepared, the one it was prepared in;
+    on a CPU device the one asked for, and nothing native runs),
+    ``info["sampling_images"]`` counts the mode-3 and mode-4 images decoded
+    natively and not flagged."""
     _check_entropy_on(entropy_on)
     _check_progressive(progressive)
     _check_restart(restart)
+    _check_sampling(sampling)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
@@ -416,10 +467,14 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         progressive = ("native" if entropy[2].native_progressive else "fallback") if on_gpu else entropy[6]
         if on_gpu:
             restart = "intervals" if entropy[2].restart_intervals else "lane"
+            sampling = "native" if entropy[2].native_sampling else "fallback"
+        else:
+            sampling = entropy[7]
     native = progressive == "native"
+    samp = sampling == "native"
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
             "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0,
-            "restart": restart, "restart_images": 0}
+            "restart": restart, "restart_images": 0, "sampling": sampling, "sampling_images": 0}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -439,11 +494,12 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     packed = None
     if on_gpu:
         _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form,
-                                                                                         progressive, restart)
+                                                                                         progressive, restart, sampling)
         status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
     else:
         _, status, hdr, coefs, offs, info["entropy_s"] = (entropy if entropy is not None else
-                                                          entropy_batch(datas, threads, "host", progressive))[:6]
+                                                          entropy_batch(datas, threads, "host", progressive,
+                                                                        sampling=sampling))[:6]
         status = list(status)
         coef_elems = coefs.numel()
     geom = None
@@ -507,7 +563,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 imgs.append(None)
                 continue
             if status[i] != 0:
-                info["fallbacks"].append((i, _refusal(C, d, status[i], native)))
+                info["fallbacks"].append((i, _refusal(C, d, status[i], native, samp)))
                 t = torch.from_numpy(host(d).copy()).to(device)
                 if full:
                     imgs.append(t)
@@ -520,6 +576,9 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         if native and n:
             prog = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_PROGRESSIVE_OFFSET // 4]
             info["progressive_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and prog[i])
+        if samp and n:
+            mode = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_MODE_OFFSET // 4]
+            info["sampling_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and mode[i] >= 3)
         # the result is complete when it is returned, whatever the batch held (the zero fill and
         # the fallbacks' copies too): a holder may hand it to a consumer on any other stream
         cur.synchronize()

@@ -1,0 +1,54 @@
+"""The 4:4:0 and 4:1:1 layouts of ``sampling="native"`` on the host, under host
+AddressSanitizer + UndefinedBehaviorSanitizer: csrc/tests/jpeg_sampling_checks.cpp (a
+stand-alone program) is built with the packer and csrc/runtime/jpeg_entropy.cpp.  For
+one file of each layout, each once plain, once with restart markers and once
+progressive, it checks that the one-lane core, the emulated sub-stream workgroup, the
+interval path and the progressive scan core, each driven from the packer's layout in
+exactly sized heap spans, give the host decoder's verdict and coefficients for the
+file, every prefix of it and every 7th byte replaced by FF, 00 and its value XOR 55.
+Host code only; the program is run directly, with nothing preloaded."""
+import os
+import shutil
+import subprocess
+
+import pytest
+from jpeg_sampling_cases import check_files
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "-distributed-machine-learning-system_amd", "csrc")
+SRCS = [os.path.join(CSRC, "tests", "jpeg_sampling_checks.cpp"), os.path.join(CSRC, "runtime", "jpeg_huff_pack.cpp"),
+        os.path.join(CSRC, "runtime", "jpeg_entropy.cpp")]
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_every_entropy_form_on_the_new_mcu_shapes_under_asan_ubsan(tmp_path):
+    files = check_files()
+    assert [n for n, _ in files] == ["440", "440-rst", "440-prog", "411", "411-rst", "411-prog"]
+    paths = []
+    for name, d in files:
+        p = tmp_path / f"{name}.jpg"
+        p.write_bytes(d)
+        paths.append(str(p))
+    exe = tmp_path / "jpeg_sampling_checks"
+    cmd = [HIPCC, "--offload-host-only", "-O1", "-g", "-std=c++17",
+           "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
+           "-Xarch_host", "-fno-sanitize-recover=all", *SRCS, "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([str(exe), *paths], capture_output=True, text=True, timeout=600, env=env)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "0 failure(s)" in r.stdout and "reached by 0)" in r.stdout
+    calls = int(r.stdout.split(" decode calls")[0].split()[-1])
+    datas = [d for _, d in files]
+    assert calls >= sum(1 + len(d) + 3 * (len(d) // 7) for d in datas)    # every prefix, every 7th byte three times
+    both_ok = int(r.stdout.split("both ok ")[1].split(",")[0])
+    both_corrupt = int(r.stdout.split("both corrupt in the scan ")[1].split(",")[0])
+    # the comparison saw both outcomes: mutants that still decode, and mutants / prefixes the entropy stage refuses
+    assert both_ok > len(datas) and both_corrupt > len(datas)
+    # and every layout of the packer took part
+    lane, par, prog, rst = (int(r.stdout.split(f"{k} ")[1].split(",")[0].split()[0])
+                            for k in ("one-lane", "sub-stream", "progressive", "interval"))
+    assert min(lane, par, prog, rst) > 100, (lane, par, prog, rst)

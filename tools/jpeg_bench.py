@@ -41,9 +41,22 @@ interval), for ``entropy_on="gpu"`` and ``"gpu_parallel"``: four arms
 alternating in one process, ``--reps`` repetitions after a warm-up of every arm,
 then the cold query of each ``--queries`` size for the same four arms.
 
+``--sampling {440,411}`` measures files of that chroma layout instead and nothing
+else.  Pillow writes neither, so each file is a Pillow file whose MCUs have the
+same block structure with its frame header rewritten to 500x375: a 4:2:2 file
+of 375x500 becomes 4:4:0 (luma 1x2), a 4:2:0 file of 256x752 becomes 4:1:1
+(luma 4x1, 16 x 47 MCUs either way).  The pictures are scrambled, the work per
+file is a photograph's.  Cold ``GpuJpegSource.get`` passes with
+``sampling="fallback"`` (every file through Pillow in ``decode_batch``'s serial
+loop) against ``"native"``, for ``entropy_on="host"`` at ``--threads``, ``"gpu"``
+and ``"gpu_parallel"``: six arms alternating in one process, ``--reps``
+repetitions after a warm-up of every arm, then the cold query of each
+``--queries`` size for the same six arms.
+
     python tools/jpeg_bench.py [--images 2000] [--threads 8] [--out profiles/jpeg_bench.log]
     python tools/jpeg_bench.py --progressive --queries 64 --out profiles/jpeg_bench_progressive.log
     python tools/jpeg_bench.py --restart 1 --queries 64,400 --out profiles/jpeg_bench_restart.log
+    python tools/jpeg_bench.py --sampling 440 --queries 64 --out profiles/jpeg_bench_sampling.log
 """
 from __future__ import annotations
 
@@ -60,12 +73,33 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def make_images(d: str, n: int, seed: int = 0, progressive: bool = False, restart_rows: int = 0) -> int:
+# --sampling: (source width, source height, Pillow subsampling, luma sampling byte) of a 500x375 file
+SAMPLING = {"440": (375, 500, 1, 0x12), "411": (256, 752, 2, 0x41)}
+
+
+def rewrite_frame(path: str, hv: int, w: int, h: int) -> None:
+    """The file's SOF0 made to say w x h with the first component sampled ``hv``."""
+    with open(path, "rb") as f:
+        d = bytearray(f.read())
+    pos = 2
+    while d[pos + 1] != 0xC0:
+        assert d[pos] == 0xFF and d[pos + 1] != 0xDA, "no baseline frame header"
+        pos += 2 + ((d[pos + 2] << 8) | d[pos + 3])
+    d[pos + 5:pos + 7] = h.to_bytes(2, "big")
+    d[pos + 7:pos + 9] = w.to_bytes(2, "big")
+    d[pos + 11] = hv
+    with open(path, "wb") as f:
+        f.write(d)
+
+
+def make_images(d: str, n: int, seed: int = 0, progressive: bool = False, restart_rows: int = 0,
+                sampling: str = "") -> int:
     """Smooth structure plus noise: files of a photograph's size (~40-60 KB), not of flat colour."""
     from PIL import Image
 
     rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:375, 0:500]
+    sw, sh, sub, hv = SAMPLING.get(sampling, (500, 375, 2, 0))
+    yy, xx = np.mgrid[0:sh, 0:sw]
     total = 0
     for i in range(n):
         ph = rng.uniform(0, 6.28, 6)
@@ -74,7 +108,9 @@ def make_images(d: str, n: int, seed: int = 0, progressive: bool = False, restar
         a = np.clip(a + rng.normal(0, 12, a.shape), 0, 255).astype(np.uint8)
         p = os.path.join(d, f"test_{i}.JPEG")
         kw = {"restart_marker_rows": restart_rows} if restart_rows else {}
-        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=2, progressive=progressive, **kw)
+        Image.fromarray(a, "RGB").save(p, "JPEG", quality=90, subsampling=sub, progressive=progressive, **kw)
+        if sampling:
+            rewrite_frame(p, hv, 500, 375)
         total += os.path.getsize(p)
     return total
 
@@ -152,6 +188,87 @@ def progressive_report(a, dev, say) -> None:
                 v = [1e3 * s for s in res[name]["s"]]
                 say(f"  {name:24s} median {np.median(v):9.2f} ms  min {min(v):9.2f}  max {max(v):9.2f} | entropy "
                     f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+
+
+def sampling_report(a, dev, say) -> None:
+    """``--sampling {440,411}``: fallback against native on files of that layout, six arms."""
+    import torch
+
+    from idunno.runtime.data import GpuJpegSource
+
+    n = a.images
+    layout = {"440": "4:4:0 (luma 1x2)", "411": "4:1:1 (luma 4x1)"}[a.sampling]
+    arms = [(f"{on:12s} {mode}", on, mode) for on in ("host", "gpu", "gpu_parallel") for mode in ("fallback", "native")]
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        x = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t, x
+
+    with tempfile.TemporaryDirectory() as d, torch.cuda.device(dev):
+        t0 = time.perf_counter()
+        nbytes = make_images(d, n, sampling=a.sampling)
+        say(f"{n} images 500x375 {layout} q90, {nbytes / n / 1024:.1f} KiB each, generated in "
+            f"{time.perf_counter() - t0:.1f} s; {torch.cuda.get_device_name(0)}; {a.threads} threads (host form)")
+
+        def source(on, mode):
+            return GpuJpegSource(dev, root=d, threads=a.threads, entropy_on=on, sampling=mode)
+
+        def passes(q, label):
+            want = None
+            for _, on, mode in arms:                                # warm-up of every arm
+                src = source(on, mode)
+                got = src.get(0, q - 1)
+                assert src.fallbacks == (q if mode == "fallback" else 0), (on, mode, src.fallbacks)
+                assert src.sampling_images == (0 if mode == "fallback" else q)
+                if mode == "native":                                # the three native forms give the same pixels
+                    assert want is None or torch.equal(got, want), on
+                    want = got
+                elif want is not None:
+                    diff = (got.int() - want.int()).abs()
+                    say(f"{label}: {on} fallback (Pillow) against native over {q} images: max |diff| "
+                        f"{int(diff.max())}, mean {float(diff.float().mean()):.4f}")
+                del got
+            del want
+            res = {name: {"s": [], "entropy_s": [], "cpu_s": []} for name, *_ in arms}
+            for r in range(a.reps):
+                for name, on, mode in arms:
+                    src = source(on, mode)
+                    c0 = time.process_time()
+                    dt, y = timed(lambda: src.get(0, q - 1))
+                    cpu = time.process_time() - c0
+                    assert src.decoded == q
+                    res[name]["s"].append(dt)
+                    res[name]["entropy_s"].append(src.seconds["entropy_s"])
+                    res[name]["cpu_s"].append(cpu)
+                    say(f"{label} rep {r}: {name:24s} {1e3 * dt:10.2f} ms  {q / dt:9.1f} img/s  entropy "
+                        f"{1e3 * src.seconds['entropy_s']:9.2f} ms  host CPU {cpu:7.3f} s")
+                    del y, src
+            return res
+
+        res = passes(n, "full pass")
+        say(f"{layout} files, cold GpuJpegSource.get of {n} images (entropy: host wall over the decode threads / "
+            "device events of the kernels; fallback decodes in Pillow after them):")
+        for name, *_ in arms:
+            v = [n / s for s in res[name]["s"]]
+            say(f"  {name:24s} median {np.median(v):9.1f} img/s  min {min(v):9.1f}  max {max(v):9.1f} | entropy "
+                f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+        for on in ("host", "gpu", "gpu_parallel"):
+            fb, nat = (np.median(res[f"{on:12s} {mode}"]["s"]) for mode in ("fallback", "native"))
+            say(f"  {on}: fallback / native = {fb / nat:.2f}x (medians)")
+        for q in [int(x) for x in a.queries.split(",") if x]:
+            q = min(q, n)
+            res = passes(q, f"query {q}")
+            say(f"{layout} files, cold query of {q} images, GpuJpegSource.get (wall):")
+            for name, *_ in arms:
+                v = [1e3 * s for s in res[name]["s"]]
+                say(f"  {name:24s} median {np.median(v):9.2f} ms  min {min(v):9.2f}  max {max(v):9.2f} | entropy "
+                    f"{1e3 * np.median(res[name]['entropy_s']):9.2f} ms | host CPU {np.median(res[name]['cpu_s']):7.3f} s")
+            for on in ("host", "gpu", "gpu_parallel"):
+                fb, nat = (np.median(res[f"{on:12s} {mode}"]["s"]) for mode in ("fallback", "native"))
+                say(f"  {on}: fallback / native = {fb / nat:.2f}x (medians)")
 
 
 def restart_report(a, dev, say) -> None:
@@ -237,6 +354,9 @@ def main(argv=None) -> int:
     ap.add_argument("--restart", type=int, default=0, metavar="ROWS", nargs="?", const=1,
                     help="measure restart-interval files only (restart_marker_rows=ROWS, default 1): restart='lane' "
                          "against 'intervals' in the two device forms")
+    ap.add_argument("--sampling", default=None, choices=sorted(SAMPLING),
+                    help="measure 4:4:0 (440) or 4:1:1 (411) files only: sampling='fallback' against 'native' in the "
+                         "three forms")
     ap.add_argument("--out", default=None, help="also write the report to this file")
     a = ap.parse_args(argv)
 
@@ -257,10 +377,12 @@ def main(argv=None) -> int:
         lines.append(s)
 
     n = a.images
-    if a.progressive or a.restart:
+    if a.progressive or a.restart or a.sampling:
         if a.restart < 0 or (a.progressive and a.restart):
             ap.error("--restart takes a positive number of MCU rows and does not combine with --progressive")
-        (progressive_report if a.progressive else restart_report)(a, dev, say)
+        if a.sampling and (a.progressive or a.restart):
+            ap.error("--sampling does not combine with --progressive or --restart")
+        (sampling_report if a.sampling else progressive_report if a.progressive else restart_report)(a, dev, say)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
