@@ -18,9 +18,10 @@ static py::dict jpeg_header_dict(const JpegHeader& h) {
   d["total_coefs"] = (int64_t)h.total_coefs;
   d["progressive"] = h.progressive != 0;
   d["nscans"] = h.nscans;
+  d["colorspace"] = h.colorspace;
   py::list comps;
   for (int c = 0; c < h.ncomp; ++c) {
-    const JpegComp& cp = h.comp[c];
+    const JpegComp& cp = h.at(c);
     py::dict e;
     e["h"] = cp.h;
     e["v"] = cp.v;
@@ -45,12 +46,13 @@ static void bytes_span(const py::handle& o, const uint8_t** p, size_t* n) {
 // (status, reason, header dict or None)
 // native_progressive: a progressive file of a supported layout is walked to EOI and accepted
 // native_sampling: 4:4:0 and 4:1:1 frames are accepted as modes 3 and 4
-py::tuple jpeg_parse(py::bytes data, bool native_progressive, bool native_sampling) {
+// native_colorspace: the header's colorspace is classified (else 0) and 1x1 CMYK / YCCK frames are accepted
+py::tuple jpeg_parse(py::bytes data, bool native_progressive, bool native_sampling, bool native_colorspace) {
   const uint8_t* p;
   size_t n;
   bytes_span(data, &p, &n);
   JpegHeader h;
-  const int st = jpeg_parse_header(n ? p : nullptr, n, &h, native_progressive, nullptr, native_sampling);
+  const int st = jpeg_parse_header(n ? p : nullptr, n, &h, native_progressive, nullptr, native_sampling, native_colorspace);
   return py::make_tuple(st, jpeg_status_name(st), st == JPEG_OK ? py::object(jpeg_header_dict(h)) : py::none());
 }
 
@@ -60,7 +62,9 @@ py::tuple jpeg_parse(py::bytes data, bool native_progressive, bool native_sampli
 // Only entries whose header parses get room in the coefficient buffer.
 // native_progressive: progressive files are decoded too (the core of jpeg_huff_prog.h).
 // native_sampling: 4:4:0 and 4:1:1 files are decoded too (modes 3 and 4).
-py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progressive, bool native_sampling) {
+// native_colorspace: RGB-coded files are classified and 1x1 CMYK / YCCK files are decoded too.
+py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progressive, bool native_sampling,
+                             bool native_colorspace) {
   const int n = (int)datas.size();
   TORCH_CHECK(threads >= 1 && threads <= 256, "threads out of range");
   std::vector<const uint8_t*> ptr(n, nullptr);
@@ -81,7 +85,8 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progre
     py::gil_scoped_release nogil;
     for (int i = 0; i < n; ++i) {
       if (ptr[i] == nullptr) continue;
-      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i], native_progressive, nullptr, native_sampling);
+      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i], native_progressive, nullptr, native_sampling,
+                                    native_colorspace);
       if (status[i] != JPEG_OK) {
         ptr[i] = nullptr;                    // keeps its parse status: not decoded
         continue;
@@ -101,7 +106,7 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progre
     std::vector<JpegHeader> h2((size_t)n);
     py::gil_scoped_release nogil;
     jpeg_decode_batch(n, ptr.data(), len.data(), h2.data(), out.data(), cap.data(), st2.data(), (int)threads,
-                      native_progressive, native_sampling);
+                      native_progressive, native_sampling, native_colorspace);
     for (int i = 0; i < n; ++i)
       if (ptr[i] != nullptr) status[i] = st2[i];
   }
@@ -112,7 +117,8 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progre
 struct JpegPlan {
   torch::Tensor desc, segs;          // device
   int64_t n_gpu = 0, nseg = 0, nblocks = 0, coef_elems = 0, plane_bytes = 0, out_bytes = 0, max_pix = 0;
-  int64_t n_exact = 0;               // of the n_gpu images, those of mode 3 / 4: their planes get the fp64 IDCT pass
+  int64_t n_exact = 0;               // of the n_gpu images, those of mode 3 / 4 or RGB / CMYK / YCCK: their planes get the fp64 IDCT pass
+  int64_t n_color = 0;               // of the n_gpu images, those with colorspace != 0: the resize kernel with their colour stages
   std::vector<int64_t> out_off;      // per entry: byte offset of its pixels in the output, -1: not on the GPU
   bool full_res = false;
 };
@@ -148,8 +154,12 @@ std::shared_ptr<JpegPlan> jpeg_plan(torch::Tensor hdr, std::vector<int64_t> stat
     if (status[i] != JPEG_OK) continue;
     const JpegHeader& h = hp[i];
     // the layout is re-derived from the frame's size and sampling; a header that disagrees is refused
-    TORCH_CHECK(h.W >= 1 && h.W <= kJpegMaxDim && h.H >= 1 && h.H <= kJpegMaxDim && (h.ncomp == 1 || h.ncomp == 3) &&
-                    h.mode >= 0 && h.mode <= 4, "jpeg_plan: bad header ", i);
+    TORCH_CHECK(h.W >= 1 && h.W <= kJpegMaxDim && h.H >= 1 && h.H <= kJpegMaxDim &&
+                    (h.ncomp == 1 || h.ncomp == 3 || h.ncomp == 4) && h.mode >= 0 && h.mode <= 4, "jpeg_plan: bad header ", i);
+    // grey: 0; three components: YCbCr or RGB; four: CMYK or YCCK, every plane full size
+    TORCH_CHECK(h.ncomp == 1 ? h.colorspace == 0 : h.ncomp == 3 ? (h.colorspace == 0 || h.colorspace == 1)
+                                                                : ((h.colorspace == 2 || h.colorspace == 3) && h.mode == 0),
+                "jpeg_plan: bad colour space ", i);
     const int hmax = h.comp[0].h, vmax = h.comp[0].v;
     TORCH_CHECK(hmax >= 1 && hmax <= 4 && vmax >= 1 && vmax <= 4, "jpeg_plan: bad sampling ", i);
     const int mcux = (h.W + 8 * hmax - 1) / (8 * hmax), mcuy = (h.H + 8 * vmax - 1) / (8 * vmax);
@@ -159,7 +169,7 @@ std::shared_ptr<JpegPlan> jpeg_plan(torch::Tensor hdr, std::vector<int64_t> stat
     std::memset(&d, 0, sizeof(d));
     int64_t co = 0;
     for (int c = 0; c < h.ncomp; ++c) {
-      const JpegComp& cp = h.comp[c];
+      const JpegComp& cp = h.at(c);
       TORCH_CHECK(cp.h >= 1 && cp.h <= hmax && cp.v >= 1 && cp.v <= vmax && hmax % cp.h == 0 && vmax % cp.v == 0 &&
                       cp.bw == mcux * cp.h && cp.bh == mcuy * cp.v && (int64_t)cp.coef_off == co,
                   "jpeg_plan: bad component layout ", i);
@@ -189,7 +199,9 @@ std::shared_ptr<JpegPlan> jpeg_plan(torch::Tensor hdr, std::vector<int64_t> stat
     d.H = h.H;
     d.ncomp = h.ncomp;
     d.mode = h.ncomp == 3 ? h.mode : 0;
-    if (d.mode >= 3) ++plan->n_exact;
+    d.colorspace = h.colorspace;
+    if (d.mode >= 3 || d.colorspace != 0) ++plan->n_exact;
+    if (d.colorspace != 0) ++plan->n_color;
     if (gp != nullptr) {
       const int64_t rw = gp[4 * i], rh = gp[4 * i + 1], left = gp[4 * i + 2], top = gp[4 * i + 3];
       TORCH_CHECK(rw >= 1 && rw <= (1 << 16) && rh >= 1 && rh <= (1 << 16) && left >= -(1 << 16) &&
@@ -262,7 +274,7 @@ void jpeg_resize_crop(const std::shared_ptr<JpegPlan>& plan, torch::Tensor plane
   TORCH_CHECK(planes.numel() >= plan->plane_bytes && out.numel() >= plan->out_bytes,
               "jpeg_resize_crop: buffer too small");
   jpeg_resize_crop_launch(planes.data_ptr<uint8_t>(), reinterpret_cast<const JpegImageDesc*>(plan->desc.data_ptr()),
-                          out.data_ptr<uint8_t>(), (int)plan->n_gpu, (int)plan->max_pix, cur_stream());
+                          out.data_ptr<uint8_t>(), (int)plan->n_gpu, (int)plan->max_pix, plan->n_color != 0, cur_stream());
   check_launch("jpeg_resize_crop");
 }
 
@@ -294,6 +306,9 @@ struct JpegHuffPacked {
   // packed with native_sampling: 4:4:0 and 4:1:1 files were accepted (modes 3 and 4 in hdr), laid out
   // like every other file of their kind; the checks before a launch then admit their luma factors
   bool native_sampling = false;
+  // packed with native_colorspace: the headers' colorspace is classified and 1x1 CMYK / YCCK files were
+  // accepted, on the one-lane or the progressive kernel; the checks before a launch then admit four components
+  bool native_colorspace = false;
 };
 
 // Parses a list of bytes / None and packs the accepted entries, GIL released.  parallel: lay the
@@ -301,8 +316,9 @@ struct JpegHuffPacked {
 // native_progressive: progressive files are accepted and laid out for the progressive kernel.
 // restart_intervals: baseline files with a restart interval get one work item per interval for the
 // interval kernel, in either layout.  native_sampling: 4:4:0 and 4:1:1 files are accepted.
+// native_colorspace: RGB-coded files are classified, 1x1 CMYK / YCCK files are accepted.
 std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bool native_progressive,
-                                               bool restart_intervals, bool native_sampling) {
+                                               bool restart_intervals, bool native_sampling, bool native_colorspace) {
   const int n = (int)datas.size();
   std::vector<const uint8_t*> ptr(n, nullptr);
   std::vector<size_t> len(n, 0);
@@ -319,13 +335,14 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   {
     py::gil_scoped_release nogil;
     jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b,
-                   parallel ? kJpegParSubBits : 0u, native_progressive, restart_intervals, native_sampling);
+                   parallel ? kJpegParSubBits : 0u, native_progressive, restart_intervals, native_sampling,
+                   native_colorspace);
   }
   const char* why = parallel ? jpeg_huff_par_check(b.desc.data(), b.par.data(), n, b.byte_total, (int64_t)b.sets.size(),
                                                    b.coef_total, b.scratch_total, kJpegParSubBits, native_progressive,
-                                                   restart_intervals, native_sampling)
+                                                   restart_intervals, native_sampling, native_colorspace)
                              : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total,
-                                               native_progressive, restart_intervals, native_sampling);
+                                               native_progressive, restart_intervals, native_sampling, native_colorspace);
   if (why == nullptr && native_progressive)
     why = jpeg_huff_prog_check(b.desc.data(), n, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   if (why == nullptr) why = jpeg_huff_rst_check(b.desc.data(), n, b.rst_items.data(), (int64_t)b.rst_items.size());
@@ -347,6 +364,7 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   static_assert(sizeof(JpegRstItem) == 4 * sizeof(int32_t), "an item is a row of four int32");
   pk->restart_intervals = restart_intervals;
   pk->native_sampling = native_sampling;
+  pk->native_colorspace = native_colorspace;
   pk->rst_items = torch::empty({(int64_t)b.rst_items.size(), 4}, torch::kInt32);
   if (!b.rst_items.empty())
     std::memcpy(pk->rst_items.data_ptr(), b.rst_items.data(), b.rst_items.size() * sizeof(JpegRstItem));
@@ -450,7 +468,7 @@ void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor b
   check_entropy_operands("jpeg_entropy_gpu", pk, bytes, coefs, status);
   const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
                                     bytes.numel(), pk->nsets, coefs.numel(), pk->native_progressive,
-                                    pk->restart_intervals, pk->native_sampling);
+                                    pk->restart_intervals, pk->native_sampling, pk->native_colorspace);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
@@ -478,7 +496,8 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
   const char* why = jpeg_huff_par_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()),
                                         reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n,
                                         bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits,
-                                        pk->native_progressive, pk->restart_intervals, pk->native_sampling);
+                                        pk->native_progressive, pk->restart_intervals, pk->native_sampling,
+                                        pk->native_colorspace);
   TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu_parallel: descriptor outside its buffer: ", why ? why : "");
   auto dev_desc = pk->desc.to(bytes.device());
   auto dev_sets = pk->sets.to(bytes.device());
@@ -556,14 +575,15 @@ void jpeg_entropy_zero(torch::Tensor coefs) {
 void bind_jpeg(py::module_& m) {
   m.def("jpeg_parse", &jpeg_parse, "JPEG markers up to SOS (native_progressive: of a progressive file up to EOI): "
         "(status, reason, header dict or None)", py::arg("data"), py::arg("native_progressive") = false,
-        py::arg("native_sampling") = false);
+        py::arg("native_sampling") = false, py::arg("native_colorspace") = false);
   m.def("jpeg_entropy_batch", &jpeg_entropy_batch,
         "baseline JPEG entropy decode of a list of bytes / None on native threads (GIL released): "
         "(status, headers, int16 coefficients on the host, offsets)", py::arg("datas"), py::arg("threads") = 8,
-        py::arg("native_progressive") = false, py::arg("native_sampling") = false);
+        py::arg("native_progressive") = false, py::arg("native_sampling") = false, py::arg("native_colorspace") = false);
   py::class_<JpegPlan, std::shared_ptr<JpegPlan>>(m, "JpegPlan")
       .def_readonly("n_gpu", &JpegPlan::n_gpu)
       .def_readonly("n_exact", &JpegPlan::n_exact)
+      .def_readonly("n_color", &JpegPlan::n_color)
       .def_readonly("nblocks", &JpegPlan::nblocks)
       .def_readonly("coef_elems", &JpegPlan::coef_elems)
       .def_readonly("plane_bytes", &JpegPlan::plane_bytes)
@@ -595,16 +615,19 @@ void bind_jpeg(py::module_& m) {
       .def_readonly("restart_intervals", &JpegHuffPacked::restart_intervals)
       .def_readonly("rst_items", &JpegHuffPacked::rst_items)
       .def_readonly("n_rst", &JpegHuffPacked::n_rst)
-      .def_readonly("native_sampling", &JpegHuffPacked::native_sampling);
+      .def_readonly("native_sampling", &JpegHuffPacked::native_sampling)
+      .def_readonly("native_colorspace", &JpegHuffPacked::native_colorspace);
   m.def("jpeg_huff_pack", &jpeg_huff_pack,
         "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage "
         "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel; restart_intervals: one work item per "
-        "restart interval for the interval kernel; native_sampling: 4:4:0 and 4:1:1 files are accepted)",
+        "restart interval for the interval kernel; native_sampling: 4:4:0 and 4:1:1 files are accepted; "
+        "native_colorspace: RGB-coded files are classified, 1x1 CMYK / YCCK files are accepted)",
         py::arg("datas"), py::arg("parallel") = false, py::arg("native_progressive") = false,
-        py::arg("restart_intervals") = false, py::arg("native_sampling") = false);
+        py::arg("restart_intervals") = false, py::arg("native_sampling") = false, py::arg("native_colorspace") = false);
   m.attr("JPEG_PROG_MAX_SCANS") = (int64_t)kJpegProgMaxScans;
   m.attr("JPEG_HEADER_PROGRESSIVE_OFFSET") = (int64_t)offsetof(JpegHeader, progressive);   // an int, in the header rows
   m.attr("JPEG_HEADER_MODE_OFFSET") = (int64_t)offsetof(JpegHeader, mode);                 // likewise
+  m.attr("JPEG_HEADER_COLORSPACE_OFFSET") = (int64_t)offsetof(JpegHeader, colorspace);     // likewise
   m.attr("JPEG_PAR_SUB_BITS") = (int64_t)kJpegParSubBits;
   m.attr("JPEG_PAR_THREADS") = (int64_t)kJpegParThreads;
   m.attr("JPEG_PAR_MAX_ROUNDS") = (int64_t)kJpegParMaxRounds;

@@ -56,11 +56,11 @@ struct JpegHuffDesc {
   int32_t set_idx;         // its JpegHuffSet in the table buffer
   int32_t gpu;
   int32_t ncomp, mcux, mcuy, restart_interval;
-  int32_t h[3], v[3], bw[3], bh[3], td[3], ta[3];
-  uint32_t coef_off[3];
+  int32_t h[4], v[4], bw[4], bh[4], td[4], ta[4];   // four: CMYK / YCCK (one-lane and progressive kernels only)
+  uint32_t coef_off[4];
   // gpu == 3 only (a progressive file, jpeg_huff_prog.h): each component's own block grid and
   // the image's range in the batch's JpegProgScan array; set_idx, td, ta, restart_interval unused
-  int32_t gw[3], gh[3];
+  int32_t gw[4], gh[4];
   int32_t scan_first, nscans;
 };
 
@@ -198,7 +198,7 @@ JH_HD inline int jpeg_huff_decode_scan(const JpegHuffDesc& d, const uint32_t* wo
                                        int16_t* coef) {
   using namespace jpeg_huff_detail;
   const int ncomp = d.ncomp;
-  if (ncomp != 1 && ncomp != 3) return kJpegHuffCorrupt;
+  if (ncomp != 1 && ncomp != 3 && ncomp != 4) return kJpegHuffCorrupt;
   if (d.mcux < 1 || d.mcuy < 1 || d.byte_len > d.byte_span) return kJpegHuffCorrupt;
   long long nblk = 0;
   for (int c = 0; c < ncomp; ++c) {
@@ -211,7 +211,7 @@ JH_HD inline int jpeg_huff_decode_scan(const JpegHuffDesc& d, const uint32_t* wo
   const uint32_t total = d.total_coefs;
   const int ri = d.restart_interval;
   int left = ri, rst = 0;
-  int pred0 = 0, pred1 = 0, pred2 = 0;
+  int pred0 = 0, pred1 = 0, pred2 = 0, pred3 = 0;
   int mx = 0, my = 0, c = 0, bx = 0, by = 0, k = 0;
   // the current component's layout and tables
   int ch = d.h[0], cv = d.v[0], cbw = d.bw[0], cbh = d.bh[0];
@@ -228,12 +228,13 @@ JH_HD inline int jpeg_huff_decode_scan(const JpegHuffDesc& d, const uint32_t* wo
     bool store = false;
     if (k == 0) {
       if (sym > 15) return kJpegHuffCorrupt;
-      int pred = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
+      int pred = c == 0 ? pred0 : (c == 1 ? pred1 : (c == 2 ? pred2 : pred3));
       if (s) pred += extend(br, s);
       if (pred < -32768 || pred > 32767) return kJpegHuffCorrupt;
       if (c == 0) pred0 = pred;
       else if (c == 1) pred1 = pred;
-      else pred2 = pred;
+      else if (c == 2) pred2 = pred;
+      else pred3 = pred;
       val = pred;
       store = true;
     } else {
@@ -276,7 +277,7 @@ JH_HD inline int jpeg_huff_decode_scan(const JpegHuffDesc& d, const uint32_t* wo
             }
             if (ri && --left == 0) {
               if (!br.restart(rst++)) return kJpegHuffCorrupt;
-              pred0 = pred1 = pred2 = 0;
+              pred0 = pred1 = pred2 = pred3 = 0;
               left = ri;
             }
           }

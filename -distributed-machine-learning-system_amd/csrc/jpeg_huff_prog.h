@@ -51,11 +51,11 @@ constexpr int kJpegProgMaxScans = 32;
 
 struct JpegProgScan {
   uint32_t byte_off;          // first entropy-coded byte of the scan inside the image's byte span
-  int32_t ncomp;              // components in the scan, 1..3; more than one: an interleaved DC scan
-  int32_t comp[3];            // their indices in the frame, ascending
+  int32_t ncomp;              // components in the scan, 1..4; more than one: an interleaved DC scan
+  int32_t comp[4];            // their indices in the frame, ascending
   int32_t ss, se, ah, al;
   int32_t restart_interval;   // in effect at this SOS: MCUs (interleaved) or blocks (one component); 0: none
-  int32_t dc_tab[3];          // per scan component: its DC table in the table buffer (DC first scans only), else -1
+  int32_t dc_tab[4];          // per scan component: its DC table in the table buffer (DC first scans only), else -1
   int32_t ac_tab;             // the AC table (AC scans only), else -1
 };
 
@@ -113,7 +113,7 @@ JH_HD inline int prog_dc_scan(const JpegHuffDesc& d, const JpegProgScan& s, Bits
   const int ri = s.restart_interval;
   const int p1 = 1 << s.al;
   int left = ri, rst = 0;
-  int pred0 = 0, pred1 = 0, pred2 = 0;
+  int pred0 = 0, pred1 = 0, pred2 = 0, pred3 = 0;
   int ux = 0, uy = 0, q = 0, bx = 0, by = 0;
   // the current component's layout and table
   int c = c0;
@@ -130,12 +130,13 @@ JH_HD inline int prog_dc_scan(const JpegHuffDesc& d, const JpegProgScan& s, Bits
     if (s.ah == 0) {
       const int sym = symbol(br, *dct);
       if (sym < 0 || sym > 15) return kJpegHuffCorrupt;
-      int pred = q == 0 ? pred0 : (q == 1 ? pred1 : pred2);
+      int pred = q == 0 ? pred0 : (q == 1 ? pred1 : (q == 2 ? pred2 : pred3));
       if (sym) pred += extend(br, sym);
       if (!fits16(pred)) return kJpegHuffCorrupt;
       if (q == 0) pred0 = pred;
       else if (q == 1) pred1 = pred;
-      else pred2 = pred;
+      else if (q == 2) pred2 = pred;
+      else pred3 = pred;
       const int val = pred * p1;                 // |pred| <= 2^15, al <= 13: no overflow of int
       if (!fits16(val)) return kJpegHuffCorrupt;
       coef[e] = (int16_t)val;
@@ -157,7 +158,7 @@ JH_HD inline int prog_dc_scan(const JpegHuffDesc& d, const JpegProgScan& s, Bits
           }
           if (ri && --left == 0) {
             if (!br.restart(rst++)) return kJpegHuffCorrupt;
-            pred0 = pred1 = pred2 = 0;
+            pred0 = pred1 = pred2 = pred3 = 0;
             left = ri;
           }
         }
@@ -305,7 +306,7 @@ JH_HD inline int jpeg_prog_decode_scan(const JpegHuffDesc& d, const JpegProgScan
                                        const JpegHuffTab* tabs, int32_t ntabs, int16_t* coef,
                                        long long* trips = nullptr) {
   using namespace jpeg_huff_detail;
-  if (d.ncomp != 1 && d.ncomp != 3) return kJpegHuffCorrupt;
+  if (d.ncomp != 1 && d.ncomp != 3 && d.ncomp != 4) return kJpegHuffCorrupt;
   if (d.mcux < 1 || d.mcuy < 1 || d.byte_len > d.byte_span || s.byte_off > d.byte_len) return kJpegHuffCorrupt;
   for (int c = 0; c < d.ncomp; ++c)
     if (d.h[c] < 1 || d.h[c] > 4 || d.v[c] < 1 || d.v[c] > 4 || d.bw[c] < 1 || d.bh[c] < 1 || d.gw[c] < 1 ||

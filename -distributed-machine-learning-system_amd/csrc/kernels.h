@@ -254,14 +254,15 @@ void softmax_topk_launch(const float* logits, int ld, int N, int rows, int k, in
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.
 struct alignas(16) JpegImageDesc {
-  unsigned short q[3][64];   // quantisation tables, natural order
-  long long plane_off[3];    // component plane: byte offset (multiple of 16), pitch[c] bytes per row, 8 * bh rows
+  unsigned short q[4][64];   // quantisation tables, natural order (the fourth: the K plane of CMYK / YCCK)
+  long long plane_off[4];    // component plane: byte offset (multiple of 16), pitch[c] bytes per row, 8 * bh rows
   long long out_off;         // byte offset of this image's [out_h][out_w][3] pixels
-  int blk_off[3];            // first 8x8 block of each component in the coefficient buffer
-  int bw[3], bh[3];          // padded block grid
-  int pitch[3];              // plane pitch: 8 * bw rounded up to 16 (a lane stores two blocks' rows at once)
-  int cw[3], ch[3];          // the plane's valid (downsampled) size: ceil(W h / hmax) x ceil(H v / vmax)
+  int blk_off[4];            // first 8x8 block of each component in the coefficient buffer
+  int bw[4], bh[4];          // padded block grid
+  int pitch[4];              // plane pitch: 8 * bw rounded up to 16 (a lane stores two blocks' rows at once)
+  int cw[4], ch[4];          // the plane's valid (downsampled) size: ceil(W h / hmax) x ceil(H v / vmax)
   int W, H, ncomp;
+  int colorspace;            // what the planes hold: 0 YCbCr or grey, 1 RGB, 2 CMYK, 3 YCCK (JpegHeader::colorspace)
   int mode;                  // chroma: 0 full size, 1 half width (h2v1), 2 half width and height (h2v2),
                              // 3 half height (h1v2, 4:4:0), 4 quarter width (h4v1, 4:1:1)
   int rw, rh;                // size after the resize (W, H: no resize)
@@ -277,13 +278,15 @@ struct JpegSeg {
 // coefficients -> uint8 component planes; nslots = 2 * (pairs of all nseg segments) block slots
 void jpeg_idct_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs, int nseg,
                       int nslots, hipStream_t st);
-// the same launch shape after jpeg_idct_launch: rewrites the planes of the images of mode 3 / 4 from an fp64
+// the same launch shape after jpeg_idct_launch: rewrites the planes of the images of mode 3 / 4 or colorspace != 0 from an fp64
 // IDCT (ties round as the float64 model's); the slots of every other image are left as they are
 void jpeg_idct_exact_launch(const int16_t* coef, uint8_t* planes, const JpegImageDesc* desc, const JpegSeg* segs,
                             int nseg, int nslots, hipStream_t st);
-// planes -> RGB, resized and cropped: nimg images of at most max_pix output pixels each
+// planes -> RGB, resized and cropped: nimg images of at most max_pix output pixels each.  color: some image of
+// the batch has colorspace != 0 (the instantiation with the RGB / CMYK / YCCK colour stages; without it the
+// kernel is the YCbCr / grey one, which reads no colorspace)
 void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,
-                             hipStream_t st);
+                             bool color, hipStream_t st);
 
 // ---- JPEG entropy stage on the device (jpeg_entropy.hip, jpeg_huff_core.h) ----
 struct JpegHuffSet;

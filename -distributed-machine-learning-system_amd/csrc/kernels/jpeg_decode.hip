@@ -15,7 +15,8 @@
 //   * jpeg_idct_exact_kernel   the planes of mode-3 / mode-4 images (4:4:0, 4:1:1) again
 //                              in fp64 over the former's output, so that their
 //                              samples round as the float64 model's; launched only
-//                              for a batch that holds such an image.
+//                              for a batch that holds such an image.  The planes of
+//                              RGB / CMYK / YCCK images (colorspace != 0) as well.
 //   * jpeg_resize_crop_kernel  one thread per output pixel: chroma "fancy"
 //                              upsampling (libjpeg's integer triangle filters for
 //                              h2v1, h2v2 and h1v2; replication for h4v1, as
@@ -24,6 +25,11 @@
 //                              horizontal pass rounded to uint8, vertical pass
 //                              rounded to uint8, centre crop.  rw == W / rh == H
 //                              makes a pass the identity (full-resolution mode).
+//                              A second instantiation, launched for a batch that
+//                              holds an image with colorspace != 0, adds the colour
+//                              stages of RGB-coded files (the planes as they are,
+//                              planes 1 and 2 upsampled like chroma), CMYK and YCCK
+//                              (Pillow's integer CMYK -> RGB).
 //
 // Both index a per-image descriptor table (kernels.h JpegImageDesc) whose offsets
 // and extents the host validated.  Plain C++ and vector stores only.
@@ -144,8 +150,10 @@ __constant__ double kIdctD[64] = {
 
 }  // namespace
 
-// The planes of the images of mode 3 and 4 once more, in fp64, over jpeg_idct_kernel's output (same slots,
-// launched after it when the batch holds such an image; every other image's slots return at once).  Their
+// The planes of the images of mode 3 and 4 and of every image with colorspace != 0 once more, in fp64, over
+// jpeg_idct_kernel's output (same slots, launched after it when the batch holds such an image; every other
+// image's slots return at once).  An RGB-coded image hands every plane on undiluted and CMYK / YCCK multiply
+// two planes, so there one level of a plane at an fp32 rounding tie is up to two levels of output.  Modes 3, 4: their
 // colour stage hands a chroma sample on undiluted (mode 4 replicates it, mode 3 filters along one axis
 // only), and R = Y + 1.402 Cr, B = Y + 1.772 Cb turn one level of chroma into two of colour, so a sample
 // whose exact value lies within fp32's reach of a rounding tie (164.5000034 was met) must round as the
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_exact_kernel(const int16_t* __r
   const int pair = slot >> 1;
   const JpegSeg sg = segs[find_seg(segs, nseg, pair)];
   const JpegImageDesc& d = desc[sg.img];
-  if (d.ncomp != 3 || d.mode < 3) return;
+  if (d.colorspace == 0 && (d.ncomp != 3 || d.mode < 3)) return;
   const int comp = sg.comp;
   const int bw = d.bw[comp], bwp = (bw + 1) >> 1;
   const int lp = pair - sg.pair_start;
@@ -207,6 +215,9 @@ struct Planes {
   int py, pc;          // pitches
   int cw, ch;          // chroma plane's valid size
   int mode, ncomp;
+  // the kColor instantiation only: the fourth plane (CMYK / YCCK, as large as the first) and JpegImageDesc::colorspace
+  const uint8_t* k;
+  int pk, cs;
 };
 
 // one upsampled chroma sample at luma position (x, y)
@@ -241,12 +252,45 @@ __device__ __forceinline__ int chroma_at(const uint8_t* __restrict__ p, int pitc
 
 __device__ __forceinline__ double to_u8d(double v) { return fmin(fmax(floor(v + 0.5), 0.0), 255.0); }
 
+// Pillow's MULDIV255: a * b / 255 rounded half up, for a, b in [0, 255]
+__device__ __forceinline__ int muldiv255(int a, int b) {
+  const int t = a * b + 128;
+  return ((t >> 8) + t) >> 8;
+}
+
 // the decoded RGB pixel (x, y) of the full-size image, each channel a whole number in [0, 255]
 // (fp64: the products have up to six decimals, and a tie must round as the float64 model's)
+// kColor: the image may be RGB-coded (P.cs 1), CMYK (2) or YCCK (3); else P.cs and P.k are not read
+template <bool kColor>
 __device__ __forceinline__ void rgb_at(const Planes& P, int x, int y, double& r, double& g, double& b) {
   const double Y = (double)P.y[(size_t)y * P.py + x];
   if (P.ncomp == 1) {
     r = g = b = Y;
+    return;
+  }
+  if (kColor && (P.cs == 1 || P.cs == 2)) {
+    int p1, p2;
+    if (P.cs == 1 && (P.mode == 1 || P.mode == 2) && P.cw <= 2) {
+      // libjpeg filters a half-width plane only when it is more than two samples wide, else it replicates;
+      // a YCbCr pixel dilutes the difference, an RGB plane is the pixel.  x >> 1 < cw, y >> 1 < ch.
+      const size_t at = (size_t)(P.mode == 2 ? y >> 1 : y) * P.pc + (x >> 1);
+      p1 = P.cb[at];
+      p2 = P.cr[at];
+    } else {
+      p1 = chroma_at(P.cb, P.pc, P.cw, P.ch, P.mode, x, y);
+      p2 = chroma_at(P.cr, P.pc, P.cw, P.ch, P.mode, x, y);
+    }
+    if (P.cs == 1) {                                   // RGB: the planes as they are
+      r = Y;
+      g = (double)p1;
+      b = (double)p2;
+      return;
+    }
+    // CMYK as Pillow reads it (inverted): C, M, Y = 255 - plane, 255 - K = plane 3
+    const int p0 = P.y[(size_t)y * P.py + x], nk = P.k[(size_t)y * P.pk + x];
+    r = (double)(nk - muldiv255(255 - p0, nk));
+    g = (double)(nk - muldiv255(255 - p1, nk));
+    b = (double)(nk - muldiv255(255 - p2, nk));
     return;
   }
   const double cb = (double)(chroma_at(P.cb, P.pc, P.cw, P.ch, P.mode, x, y) - 128);
@@ -254,6 +298,12 @@ __device__ __forceinline__ void rgb_at(const Planes& P, int x, int y, double& r,
   r = to_u8d(Y + 1.402 * cr);
   g = to_u8d(Y - 0.344136 * cb - 0.714136 * cr);
   b = to_u8d(Y + 1.772 * cb);
+  if (kColor && P.cs == 3) {                           // YCCK: C, M, Y = the R', G', B' of planes 0..2
+    const int nk = P.k[(size_t)y * P.pk + x];
+    r = (double)(nk - muldiv255((int)r, nk));
+    g = (double)(nk - muldiv255((int)g, nk));
+    b = (double)(nk - muldiv255((int)b, nk));
+  }
 }
 
 // Pillow's BILINEAR taps of output position o on an axis resized in -> out
@@ -275,17 +325,18 @@ struct Axis {
 };
 
 // row y of the horizontally resized image at column rx, rounded to uint8
+template <bool kColor>
 __device__ __forceinline__ void hpass_at(const Planes& P, const Axis& ax, bool ident, int rx, int y, double& r,
                                          double& g, double& b) {
   if (ident) {
-    rgb_at(P, rx, y, r, g, b);
+    rgb_at<kColor>(P, rx, y, r, g, b);
     return;
   }
   double fr, fg, fb;
   double ar = 0.0, ag = 0.0, ab = 0.0, ws = 0.0;
   for (int x = ax.lo; x < ax.hi; ++x) {
     const double w = ax.weight(x);
-    rgb_at(P, x, y, fr, fg, fb);
+    rgb_at<kColor>(P, x, y, fr, fg, fb);
     ar += w * fr;
     ag += w * fg;
     ab += w * fb;
@@ -299,6 +350,7 @@ __device__ __forceinline__ void hpass_at(const Planes& P, const Axis& ax, bool i
 
 }  // namespace
 
+template <bool kColor>
 __global__ __launch_bounds__(256) void jpeg_resize_crop_kernel(const uint8_t* __restrict__ planes,
                                                                const JpegImageDesc* __restrict__ desc,
                                                                uint8_t* __restrict__ out) {
@@ -315,23 +367,34 @@ __global__ __launch_bounds__(256) void jpeg_resize_crop_kernel(const uint8_t* __
     P.py = d.pitch[0];
     P.ncomp = d.ncomp;
     P.mode = d.mode;
-    const int cc = d.ncomp == 3 ? 1 : 0;
+    const bool multi = kColor ? d.ncomp >= 3 : d.ncomp == 3;
+    const int cc = multi ? 1 : 0;
     P.cb = planes + d.plane_off[cc];
-    P.cr = planes + d.plane_off[d.ncomp == 3 ? 2 : 0];
+    P.cr = planes + d.plane_off[multi ? 2 : 0];
+    P.cs = 0;
+    P.k = P.y;
+    P.pk = P.py;
+    if (kColor) {
+      P.cs = d.colorspace;
+      if (d.ncomp == 4) {
+        P.k = planes + d.plane_off[3];
+        P.pk = d.pitch[3];
+      }
+    }
     P.pc = d.pitch[cc];
     P.cw = d.cw[cc];
     P.ch = d.ch[cc];
     const bool hid = d.rw == d.W, vid = d.rh == d.H;
     const Axis ax(rx, d.W, d.rw);
     if (vid) {
-      hpass_at(P, ax, hid, rx, ry, r, g, b);
+      hpass_at<kColor>(P, ax, hid, rx, ry, r, g, b);
     } else {
       const Axis ay(ry, d.H, d.rh);
       double ar = 0.0, ag = 0.0, ab = 0.0, ws = 0.0;
       for (int y = ay.lo; y < ay.hi; ++y) {
         const double w = ay.weight(y);
         double hr, hg, hb;
-        hpass_at(P, ax, hid, rx, y, hr, hg, hb);
+        hpass_at<kColor>(P, ax, hid, rx, y, hr, hg, hb);
         ar += w * hr;
         ag += w * hg;
         ab += w * hb;
@@ -364,10 +427,11 @@ void jpeg_idct_exact_launch(const int16_t* coef, uint8_t* planes, const JpegImag
 }
 
 void jpeg_resize_crop_launch(const uint8_t* planes, const JpegImageDesc* desc, uint8_t* out, int nimg, int max_pix,
-                             hipStream_t st) {
+                             bool color, hipStream_t st) {
   if (nimg <= 0 || max_pix <= 0) return;
-  hipLaunchKernelGGL(jpeg_resize_crop_kernel, dim3((unsigned)((max_pix + 255) / 256), (unsigned)nimg), dim3(256), 0,
-                     st, planes, desc, out);
+  const dim3 grid((unsigned)((max_pix + 255) / 256), (unsigned)nimg);
+  if (color) hipLaunchKernelGGL(jpeg_resize_crop_kernel<true>, grid, dim3(256), 0, st, planes, desc, out);
+  else hipLaunchKernelGGL(jpeg_resize_crop_kernel<false>, grid, dim3(256), 0, st, planes, desc, out);
 }
 
 }  // namespace idunno

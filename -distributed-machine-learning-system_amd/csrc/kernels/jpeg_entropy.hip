@@ -20,6 +20,10 @@
 // (restart="intervals", last) decodes the baseline files with a restart interval,
 // one lane per interval, in either device form as well.
 //
+// Four-component files (CMYK / YCCK, colorspace="auto") are decoded by the first and the
+// third kernel only: the packer never marks one for the sub-stream or the interval kernel,
+// whose state and item layouts stay those of one and three components.
+//
 // The host (bind_jpeg.cpp jpeg_entropy_gpu / jpeg_entropy_gpu_parallel) has checked every descriptor against
 // the three buffers with jpeg_huff_check before the launch (the progressive entries'
 // scan ranges and table indices with jpeg_huff_prog_check, the restart-interval

@@ -12,6 +12,10 @@
 // With native_sampling the parser also accepts the 4:4:0 (luma 1x2) and 4:1:1
 // (luma 4x1) layouts as modes 3 and 4; the decode loops are the same, they take
 // every h, v in 1..4 from the header.
+//
+// With native_colorspace the marker walk also records JFIF APP0, Adobe APP14 and the
+// component ids, classifies the colour model as libjpeg does (JpegHeader::colorspace) and
+// accepts four components sampled 1x1; the decode loops run over ncomp as before.
 #include "jpeg_entropy.h"
 
 #include <algorithm>
@@ -81,7 +85,7 @@ struct Tables {
 };
 
 struct Scan {
-  int td[3], ta[3];
+  int td[4], ta[4];
 };
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
@@ -130,15 +134,33 @@ int script_tab(const RawTabs& raw, int slot, JpegProgScript* script) {
 
 // native: an SOF2 frame is walked to EOI (script, when given, receives its scans)
 // sampling: luma 1x2 and 4x1 over 1x1 chroma are modes 3 and 4, not JPEG_UNSUPPORTED_SAMPLING
+// color: JFIF / Adobe / component ids decide hdr->colorspace, four 1x1 components are taken
 int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, bool native = false,
-          JpegProgScript* script = nullptr, bool sampling = false) {
+          JpegProgScript* script = nullptr, bool sampling = false, bool color = false) {
   if (data == nullptr || n == 0) return JPEG_EMPTY;
   if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_NOT_JPEG;
   std::memset(hdr, 0, sizeof(*hdr));
   if (script != nullptr) *script = JpegProgScript{};
   bool have_sof = false;
-  int comp_id[3] = {0, 0, 0};
-  bool latched[3] = {false, false, false};
+  int comp_id[4] = {0, 0, 0, 0};
+  bool latched[4] = {false, false, false, false};
+  bool jfif = false, adobe = false;
+  int adobe_transform = 0;
+  // libjpeg's rules, applied at the first SOS (every APPn in front of it has been seen): false: refused
+  auto classify = [&]() {
+    hdr->colorspace = 0;
+    if (!color) return true;
+    if (hdr->ncomp == 3) {
+      if (jfif) return true;
+      if (adobe) hdr->colorspace = adobe_transform == 0 ? 1 : 0;
+      else if (comp_id[0] == 'R' && comp_id[1] == 'G' && comp_id[2] == 'B') hdr->colorspace = 1;
+    } else if (hdr->ncomp == 4) {
+      if (!adobe || adobe_transform == 0) hdr->colorspace = 2;
+      else if (adobe_transform == 2) hdr->colorspace = 3;
+      else return false;
+    }
+    return true;
+  };
   std::vector<RawTabs> rawv(native ? 1 : 0);            // off the stack
   size_t pos = 2;
   for (;;) {
@@ -167,7 +189,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
         if (have_sof || slen < 6) return JPEG_CORRUPT;
         if (seg[0] != 8) return JPEG_UNSUPPORTED_PRECISION;
         const int H = be16(seg + 1), W = be16(seg + 3), nf = seg[5];
-        if (nf != 1 && nf != 3) return nf == 0 ? JPEG_CORRUPT : JPEG_UNSUPPORTED_COMPONENTS;
+        if (nf != 1 && nf != 3 && !(color && nf == 4)) return nf == 0 ? JPEG_CORRUPT : JPEG_UNSUPPORTED_COMPONENTS;
         if (slen != (size_t)(6 + 3 * nf) || W == 0 || H == 0) return JPEG_CORRUPT;
         if (W > kJpegMaxDim || H > kJpegMaxDim) return JPEG_UNSUPPORTED_SIZE;
         hdr->W = W;
@@ -178,9 +200,9 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           const int hv = seg[7 + 3 * c], tq = seg[8 + 3 * c];
           const int h = hv >> 4, v = hv & 15;
           if (h < 1 || h > 4 || v < 1 || v > 4 || tq > 3) return JPEG_CORRUPT;
-          hdr->comp[c].h = nf == 1 ? 1 : h;             // one component: never interleaved
-          hdr->comp[c].v = nf == 1 ? 1 : v;
-          hdr->comp[c].qidx = tq;
+          hdr->at(c).h = nf == 1 ? 1 : h;             // one component: never interleaved
+          hdr->at(c).v = nf == 1 ? 1 : v;
+          hdr->at(c).qidx = tq;
         }
         if (nf == 3) {
           const JpegComp* cp = hdr->comp;
@@ -192,13 +214,16 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           else if (sampling && cp[1].h == 1 && cp[1].v == 1 && cp[0].h == 4 && cp[0].v == 1) hdr->mode = 4;
           else return JPEG_UNSUPPORTED_SAMPLING;
         }
+        if (nf == 4)                                     // CMYK / YCCK: as libjpeg writes them, every component 1x1
+          for (int c = 0; c < 4; ++c)
+            if (hdr->at(c).h != 1 || hdr->at(c).v != 1) return JPEG_UNSUPPORTED_SAMPLING;
         hdr->hmax = hdr->comp[0].h;
         hdr->vmax = hdr->comp[0].v;
         hdr->mcux = (W + 8 * hdr->hmax - 1) / (8 * hdr->hmax);
         hdr->mcuy = (H + 8 * hdr->vmax - 1) / (8 * hdr->vmax);
         uint32_t off = 0;
         for (int c = 0; c < nf; ++c) {
-          JpegComp& cp = hdr->comp[c];
+          JpegComp& cp = hdr->at(c);
           cp.bw = hdr->mcux * cp.h;
           cp.bh = hdr->mcuy * cp.v;
           cp.coef_off = off;
@@ -252,7 +277,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           JpegProgScan s;
           std::memset(&s, 0, sizeof(s));
           s.ncomp = ns;
-          s.ac_tab = s.dc_tab[0] = s.dc_tab[1] = s.dc_tab[2] = -1;
+          s.ac_tab = s.dc_tab[0] = s.dc_tab[1] = s.dc_tab[2] = s.dc_tab[3] = -1;
           const uint8_t* t = seg + 1 + 2 * ns;
           s.ss = t[0];
           s.se = t[1];
@@ -260,7 +285,7 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           s.al = t[2] & 15;
           if (s.se > 63 || s.ss > s.se || s.al > 13 || (s.ah != 0 && s.ah != s.al + 1)) return JPEG_CORRUPT;
           if (s.ss == 0 ? s.se != 0 : ns != 1) return JPEG_CORRUPT;
-          int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+          int td[4] = {0, 0, 0, 0}, ta[4] = {0, 0, 0, 0};
           for (int c = 0; c < ns; ++c) {
             int ci = -1;
             for (int f = 0; f < hdr->ncomp; ++f)
@@ -273,11 +298,12 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
             // only the table the scan decodes with has to exist: DC first scans a DC table, AC scans an AC table
             if (s.ss == 0 ? (s.ah == 0 && raw.key[td[c]].empty()) : raw.key[4 + ta[c]].empty()) return JPEG_CORRUPT;
             if (!latched[ci]) {
-              if (!tb->qdef[hdr->comp[ci].qidx]) return JPEG_CORRUPT;
-              std::memcpy(hdr->comp[ci].q, tb->q[hdr->comp[ci].qidx], sizeof(hdr->comp[ci].q));
+              if (!tb->qdef[hdr->at(ci).qidx]) return JPEG_CORRUPT;
+              std::memcpy(hdr->at(ci).q, tb->q[hdr->at(ci).qidx], sizeof(hdr->at(ci).q));
               latched[ci] = true;
             }
           }
+          if (hdr->nscans == 0 && !classify()) return JPEG_UNSUPPORTED_COMPONENTS;
           if (hdr->nscans == 0) hdr->scan_pos = (uint32_t)pos;
           if (script != nullptr) {
             if (hdr->nscans == 0) script->first_pos = (uint32_t)pos;
@@ -304,16 +330,26 @@ int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, 
           sc->ta[c] = t & 15;
           if (sc->td[c] > 3 || sc->ta[c] > 3) return JPEG_CORRUPT;
           if (!tb->dc[sc->td[c]].defined || !tb->ac[sc->ta[c]].defined) return JPEG_CORRUPT;
-          if (!tb->qdef[hdr->comp[c].qidx]) return JPEG_CORRUPT;
-          std::memcpy(hdr->comp[c].q, tb->q[hdr->comp[c].qidx], sizeof(hdr->comp[c].q));
+          if (!tb->qdef[hdr->at(c).qidx]) return JPEG_CORRUPT;
+          std::memcpy(hdr->at(c).q, tb->q[hdr->at(c).qidx], sizeof(hdr->at(c).q));
         }
         const uint8_t* t = seg + 1 + 2 * ns;
         if (t[0] != 0 || t[1] != 63 || t[2] != 0) return JPEG_CORRUPT;
+        if (!classify()) return JPEG_UNSUPPORTED_COMPONENTS;
         hdr->scan_pos = (uint32_t)pos;
         hdr->nscans = 1;
         return JPEG_OK;
       }
-      default:                                           // APPn, COM and anything else with a length
+      case 0xE0:                                         // APP0: "JFIF\0" and at least the 14 bytes libjpeg asks for
+        if (slen >= 14 && std::memcmp(seg, "JFIF\0", 5) == 0) jfif = true;
+        break;
+      case 0xEE:                                         // APP14: "Adobe", version, flags0, flags1, transform
+        if (slen >= 12 && std::memcmp(seg, "Adobe", 5) == 0) {
+          adobe = true;
+          adobe_transform = seg[11];
+        }
+        break;
+      default:                                           // other APPn, COM and anything else with a length
         break;
     }
   }
@@ -449,10 +485,10 @@ const char* jpeg_status_name(int status) {
 }
 
 int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive, JpegProgScript* script,
-                      bool native_sampling) {
+                      bool native_sampling, bool native_colorspace) {
   std::vector<Tables> tb(1);                             // ~9 KB: off the stack
   Scan sc;
-  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script, native_sampling);
+  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script, native_sampling, native_colorspace);
 }
 
 void jpeg_prog_frame_desc(const JpegHeader& h, JpegHuffDesc* d) {
@@ -460,8 +496,8 @@ void jpeg_prog_frame_desc(const JpegHeader& h, JpegHuffDesc* d) {
   d->ncomp = h.ncomp;
   d->mcux = h.mcux;
   d->mcuy = h.mcuy;
-  for (int c = 0; c < h.ncomp && c < 3; ++c) {
-    const JpegComp& cp = h.comp[c];
+  for (int c = 0; c < h.ncomp && c < 4; ++c) {
+    const JpegComp& cp = h.at(c);
     d->h[c] = cp.h;
     d->v[c] = cp.v;
     d->bw[c] = cp.bw;
@@ -495,12 +531,13 @@ int decode_progressive(const uint8_t* data, size_t n, const JpegHeader& hdr, con
 }  // namespace
 
 int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, bool native_progressive,
-                bool native_sampling) {
+                bool native_sampling, bool native_colorspace) {
   std::vector<Tables> tbv(1);
   Tables& tb = tbv[0];
   Scan sc;
   JpegProgScript script;
-  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr, native_sampling);
+  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr, native_sampling,
+                       native_colorspace);
   if (st != JPEG_OK) return st;
   if (out == nullptr || (size_t)hdr->total_coefs > out_cap) return JPEG_BUFFER_TOO_SMALL;
   std::memset(out, 0, (size_t)hdr->total_coefs * sizeof(int16_t));
@@ -509,7 +546,7 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
   br.data = data;
   br.p = hdr->scan_pos;
   br.end = n;
-  int pred[3] = {0, 0, 0};
+  int pred[4] = {0, 0, 0, 0};
   const int ri = hdr->restart_interval;
   int left = ri, rst = 0;
   for (int my = 0; my < hdr->mcuy; ++my) {
@@ -517,13 +554,13 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
       if (ri) {
         if (left == 0) {
           if (!br.restart(rst++)) return JPEG_CORRUPT;
-          pred[0] = pred[1] = pred[2] = 0;
+          pred[0] = pred[1] = pred[2] = pred[3] = 0;
           left = ri;
         }
         --left;
       }
       for (int c = 0; c < hdr->ncomp; ++c) {
-        const JpegComp& cp = hdr->comp[c];
+        const JpegComp& cp = hdr->at(c);
         for (int by = 0; by < cp.v; ++by) {
           for (int bx = 0; bx < cp.h; ++bx) {
             const size_t b = (size_t)(my * cp.v + by) * (size_t)cp.bw + (size_t)(mx * cp.h + bx);
@@ -539,14 +576,15 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
 
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
                        int16_t* const* out, const size_t* out_cap, int* status, int nthreads,
-                       bool native_progressive, bool native_sampling) {
+                       bool native_progressive, bool native_sampling, bool native_colorspace) {
   std::atomic<int> next{0};
   auto work = [&]() {
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) return;
       status[i] = data[i] == nullptr ? (int)JPEG_EMPTY
-                                     : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive, native_sampling);
+                                     : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive, native_sampling,
+                                                   native_colorspace);
     }
   };
   const int nt = std::max(1, std::min(nthreads, n));

@@ -11,7 +11,10 @@
 //
 // Progressive files (SOF2) are refused unless a caller passes native_progressive;
 // then they decode into the same layout (../jpeg_huff_prog.h).  The 4:4:0 and
-// 4:1:1 chroma layouts are refused unless a caller passes native_sampling.
+// 4:1:1 chroma layouts are refused unless a caller passes native_sampling.  Without
+// native_colorspace a 3-component file is taken for YCbCr whatever its markers say and a
+// 4-component one is refused; with it the JFIF / Adobe markers and the component ids
+// classify the file as libjpeg does (JpegHeader::colorspace) and 1x1 CMYK / YCCK is decoded.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -30,9 +33,9 @@ enum JpegStatus : int {
   JPEG_UNSUPPORTED_PROGRESSIVE = 4,
   JPEG_UNSUPPORTED_ARITHMETIC = 5,
   JPEG_UNSUPPORTED_PRECISION = 6,   // 12-bit samples
-  JPEG_UNSUPPORTED_COMPONENTS = 7,  // 4 components (CMYK / YCCK), or 2
+  JPEG_UNSUPPORTED_COMPONENTS = 7,  // 4 components (CMYK / YCCK), or 2; with native_colorspace: 2, or 4 with an Adobe transform not 0 / 2
   JPEG_UNSUPPORTED_QUANT16 = 8,     // 16-bit quantisation tables
-  JPEG_UNSUPPORTED_SAMPLING = 9,    // not 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2); with native_sampling: nor 4:4:0 (1x2) / 4:1:1 (4x1)
+  JPEG_UNSUPPORTED_SAMPLING = 9,    // not 4:4:4 / 4:2:2 (2x1) / 4:2:0 (2x2); with native_sampling: nor 4:4:0 (1x2) / 4:1:1 (4x1); 4 components not all 1x1
   JPEG_UNSUPPORTED_SIZE = 10,       // above 4096 x 4096
   JPEG_UNSUPPORTED_MULTISCAN = 11,  // baseline with one scan per component; progressive above kJpegProgMaxScans
   JPEG_UNSUPPORTED_SOF = 12,        // lossless / hierarchical frames
@@ -54,7 +57,7 @@ struct JpegComp {
 
 struct JpegHeader {
   int W, H;
-  int ncomp;           // 1 or 3
+  int ncomp;           // 1 or 3; with native_colorspace also 4
   int hmax, vmax;
   int mode;            // chroma layout: 0 as luma, 1 half width (h2v1), 2 half width and height (h2v2);
                        // with native_sampling also 3 half height (h1v2, 4:4:0), 4 quarter width (h4v1, 4:1:1)
@@ -62,9 +65,14 @@ struct JpegHeader {
   int restart_interval;
   uint32_t total_coefs;   // int16 elements the coefficient buffer must hold
   uint32_t scan_pos;      // byte offset of the entropy-coded data
-  JpegComp comp[3];
+  JpegComp comp[3];       // components 0..2; the fourth: comp_k below, at(c) reaches all four
   int progressive;        // 1: an SOF2 frame, accepted because the caller asked for native progressive decoding
   int nscans;             // its scans (1 for a baseline file)
+  int colorspace;         // what the samples are: 0 YCbCr or grey, 1 RGB, 2 CMYK, 3 YCCK; always 0 without native_colorspace
+  JpegComp comp_k;        // the fourth component (K of CMYK / YCCK): behind the ints, so that every field in front of
+                          // it keeps the offset it has in the header rows callers read (mode, progressive)
+  JpegComp& at(int c) { return c < 3 ? comp[c] : comp_k; }
+  const JpegComp& at(int c) const { return c < 3 ? comp[c] : comp_k; }
 };
 
 // The scan script of a progressive file, in the form jpeg_huff_prog.h decodes: what
@@ -88,8 +96,17 @@ struct JpegProgScript {
 // native_sampling: a 3-component frame whose chroma components are both 1x1 and
 // whose luma is 1x2 or 4x1 is accepted as mode 3 or 4; every other layout beyond
 // modes 0..2 stays JPEG_UNSUPPORTED_SAMPLING.
+// native_colorspace: the colour model is read as libjpeg reads it.  Three components: YCbCr
+// when a JFIF APP0 was seen; else, when an Adobe APP14 was seen (at least 12 bytes, starting
+// with "Adobe"), RGB for its transform byte 0 and YCbCr otherwise; else RGB for the component
+// ids 'R','G','B' and YCbCr for anything else.  Four components, all sampled 1x1 (mode 0; any
+// other sampling is JPEG_UNSUPPORTED_SAMPLING), baseline or progressive: CMYK without an
+// Adobe segment or with transform 0, YCCK with transform 2, JPEG_UNSUPPORTED_COMPONENTS for
+// any other transform.  Without the flag hdr->colorspace is 0 and every 3-component file is
+// decoded as YCbCr downstream, an RGB-coded one included.
 int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive = false,
-                      JpegProgScript* script = nullptr, bool native_sampling = false);
+                      JpegProgScript* script = nullptr, bool native_sampling = false,
+                      bool native_colorspace = false);
 
 // The frame layout of *hdr in a JpegHuffDesc (ncomp, MCU grid, per component
 // sampling, padded grid, own grid, coefficient offsets, total_coefs): what
@@ -100,15 +117,16 @@ void jpeg_prog_frame_desc(const JpegHeader& hdr, JpegHuffDesc* d);
 // reads outside data[0, n) nor writes outside out[0, out_cap).
 // native_progressive: a progressive file is decoded with the core of
 // jpeg_huff_prog.h on a word-aligned copy of its scans; baseline files are
-// decoded as without it.  native_sampling: as for jpeg_parse_header.
+// decoded as without it.  native_sampling, native_colorspace: as for jpeg_parse_header.
 int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap,
-                bool native_progressive = false, bool native_sampling = false);
+                bool native_progressive = false, bool native_sampling = false, bool native_colorspace = false);
 
 // Decodes n images on a pool of `nthreads` std::threads (never derived from
 // the machine's CPU count).  Image i with data[i] == nullptr is skipped with
 // JPEG_EMPTY.  status[i] and hdr[i] are written for every i.
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
                        int16_t* const* out, const size_t* out_cap, int* status, int nthreads = 8,
-                       bool native_progressive = false, bool native_sampling = false);
+                       bool native_progressive = false, bool native_sampling = false,
+                       bool native_colorspace = false);
 
 }  // namespace idunno

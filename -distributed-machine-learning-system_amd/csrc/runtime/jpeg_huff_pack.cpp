@@ -21,7 +21,7 @@ struct RawTab {
 
 struct RawSet {
   RawTab t[8];            // dc 0..3, ac 0..3
-  int td[3], ta[3];
+  int td[4], ta[4];
 };
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
@@ -142,7 +142,7 @@ size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
                     JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive, bool restart_intervals,
-                    bool native_sampling) {
+                    bool native_sampling, bool native_colorspace) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
   out->scans.clear();
@@ -163,7 +163,8 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       status[i] = JPEG_EMPTY;
       continue;
     }
-    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script, native_sampling);
+    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script, native_sampling,
+                                  native_colorspace);
     if (status[i] != JPEG_OK) continue;
     const JpegHeader& h = hdr[i];
     if (h.progressive) {
@@ -187,7 +188,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       d.scan_first = (int32_t)out->scans.size();
       d.nscans = (int32_t)script.scans.size();
       for (JpegProgScan s : script.scans) {
-        for (int c = 0; c < 3; ++c)
+        for (int c = 0; c < 4; ++c)
           if (s.dc_tab[c] >= 0) s.dc_tab[c] = remap[(size_t)s.dc_tab[c]];
         if (s.ac_tab >= 0) s.ac_tab = remap[(size_t)s.ac_tab];
         out->scans.push_back(s);
@@ -224,7 +225,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
     d.set_idx = it->second;
     d.byte_off = out->byte_total;
     d.byte_len = (uint32_t)(len[i] - h.scan_pos);
-    if (par_sub_bits && h.restart_interval == 0) {
+    if (par_sub_bits && h.restart_interval == 0 && h.ncomp != 4) {   // four components: the one-lane kernel
       const size_t k = destuff(data[i] + h.scan_pos, len[i] - h.scan_pos, nullptr, (size_t)-1);
       if (k < kJpegParMaxBits / 8u) {
         JpegParDesc& p = out->par[(size_t)i];
@@ -232,7 +233,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
         d.byte_len = (uint32_t)k;
         p.bit_len = (uint32_t)k * 8u;
         p.bpm = 0;
-        for (int c = 0; c < h.ncomp; ++c) p.bpm += h.comp[c].h * h.comp[c].v;
+        for (int c = 0; c < h.ncomp; ++c) p.bpm += h.at(c).h * h.at(c).v;
         p.total_blocks = (uint32_t)h.mcux * (uint32_t)h.mcuy * (uint32_t)p.bpm;
         p.scan_pos = h.scan_pos;
         p.scratch_off = out->scratch_total;
@@ -249,15 +250,15 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
     d.mcuy = h.mcuy;
     d.restart_interval = h.restart_interval;
     for (int c = 0; c < h.ncomp; ++c) {
-      d.h[c] = h.comp[c].h;
-      d.v[c] = h.comp[c].v;
-      d.bw[c] = h.comp[c].bw;
-      d.bh[c] = h.comp[c].bh;
-      d.coef_off[c] = h.comp[c].coef_off;
+      d.h[c] = h.at(c).h;
+      d.v[c] = h.at(c).v;
+      d.bw[c] = h.at(c).bw;
+      d.bh[c] = h.at(c).bh;
+      d.coef_off[c] = h.at(c).coef_off;
       d.td[c] = rs.td[c];
       d.ta[c] = rs.ta[c];
     }
-    if (restart_intervals && d.gpu == 1 && h.restart_interval > 0 && h.mcux >= 1 && h.mcuy >= 1) {
+    if (restart_intervals && d.gpu == 1 && h.restart_interval > 0 && h.mcux >= 1 && h.mcuy >= 1 && h.ncomp != 4) {
       // one item per interval: the byte after each in-sequence RSTn, found by the reader's byte rules
       const int64_t ri = h.restart_interval;
       const int64_t need = ((int64_t)h.mcux * h.mcuy + ri - 1) / ri - 1;
@@ -314,7 +315,7 @@ namespace {
 
 const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
                       int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog, bool allow_rst,
-                      bool allow_sampling) {
+                      bool allow_sampling, bool allow_colorspace) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
   int64_t scratch_at = 0;
   if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
@@ -331,7 +332,7 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
     if (d.coef_base < coef_at || d.coef_base % 64 != 0 || d.coef_base + (int64_t)d.total_coefs > coef_cap)
       return "coefficient span outside the coefficient buffer";
     coef_at = d.coef_base + (int64_t)d.total_coefs;
-    if ((d.ncomp != 1 && d.ncomp != 3) || d.mcux < 1 || d.mcuy < 1 || d.mcux > kJpegMaxDim / 8 + 1 ||
+    if ((d.ncomp != 1 && d.ncomp != 3 && d.ncomp != 4) || d.mcux < 1 || d.mcuy < 1 || d.mcux > kJpegMaxDim / 8 + 1 ||
         d.mcuy > kJpegMaxDim / 8 + 1 || d.restart_interval < 0 || d.restart_interval > 65535)
       return "frame";
     int64_t co = 0;
@@ -346,6 +347,12 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
     if (!allow_sampling && d.ncomp == 3 && d.h[1] == 1 && d.v[1] == 1 && d.h[2] == 1 && d.v[2] == 1 &&
         ((d.h[0] == 1 && d.v[0] == 2) || (d.h[0] == 4 && d.v[0] == 1)))
       return "sampling layout of a batch planned without native_sampling";
+    if (d.ncomp == 4) {
+      if (!allow_colorspace) return "four components in a batch planned without native_colorspace";
+      if (d.gpu == 2 || d.gpu == 4) return "four components outside the one-lane and progressive kernels";
+      for (int c = 0; c < 4; ++c)
+        if (d.h[c] != 1 || d.v[c] != 1) return "four components not all 1x1";
+    }
     if (d.gpu == 4 && d.restart_interval < 1) return "restart interval";
     if (d.gpu == 2) {
       const JpegParDesc& p = par[i];
@@ -365,15 +372,17 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
 }  // namespace
 
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog, bool allow_rst, bool allow_sampling) {
-  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst, allow_sampling);
+                            bool allow_prog, bool allow_rst, bool allow_sampling, bool allow_colorspace) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst, allow_sampling,
+                   allow_colorspace);
 }
 
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog, bool allow_rst, bool allow_sampling) {
+                                bool allow_prog, bool allow_rst, bool allow_sampling, bool allow_colorspace) {
   if (par == nullptr) return "no sub-stream descriptors";
-  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst, allow_sampling);
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst, allow_sampling,
+                   allow_colorspace);
 }
 
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
@@ -386,7 +395,7 @@ const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProg
         (int64_t)d.scan_first + d.nscans > nscans)
       return "scan range outside the scan buffer";
     scan_at = (int64_t)d.scan_first + d.nscans;
-    if (d.ncomp != 1 && d.ncomp != 3) return "frame";
+    if (d.ncomp != 1 && d.ncomp != 3 && d.ncomp != 4) return "frame";
     for (int c = 0; c < d.ncomp; ++c)
       if (d.gw[c] < 1 || d.gh[c] < 1 || d.gw[c] > d.bw[c] || d.gh[c] > d.bh[c] || d.gw[c] <= d.bw[c] - d.h[c] ||
           d.gh[c] <= d.bh[c] - d.v[c])

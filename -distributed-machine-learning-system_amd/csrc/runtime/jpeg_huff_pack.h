@@ -58,9 +58,14 @@ struct JpegHuffBatch {
 // one-lane kernel gives the verdict.  gpu == 2 and gpu == 3 entries are untouched.
 // native_sampling: passed to jpeg_parse_header, so 4:4:0 and 4:1:1 files (modes 3 and 4)
 // are accepted and laid out like every other file of their kind (gpu 1 to 4).
+// native_colorspace: passed to jpeg_parse_header, so hdr[i].colorspace is classified and 1x1
+// four-component files (CMYK, YCCK) are accepted.  A four-component file gets gpu == 1, or
+// gpu == 3 when progressive, in either form and whatever restart_intervals says: the
+// sub-stream and interval kernels keep to one and three components.  RGB-coded
+// three-component files are laid out like their YCbCr twins.
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
                     JpegHuffBatch* out, uint32_t par_sub_bits = 0, bool native_progressive = false,
-                    bool restart_intervals = false, bool native_sampling = false);
+                    bool restart_intervals = false, bool native_sampling = false, bool native_colorspace = false);
 
 // Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
 // zeroes the padding between them.  A gpu == 2 entry gets its de-stuffed words
@@ -76,15 +81,19 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 // allow_rst: gpu == 4 entries are taken (spans, frame, a restart interval; their items: jpeg_huff_rst_check).
 // allow_sampling: a 3-component entry may have luma 1x2 or 4x1 over 1x1 chroma (modes 3 and 4); without it
 // such an entry, which only a batch planned with native_sampling holds, is refused.
+// allow_colorspace: an entry may have four components, all 1x1, with gpu == 1 or 3; without it such an
+// entry, which only a batch planned with native_colorspace holds, is refused.
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false);
+                            bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false,
+                            bool allow_colorspace = false);
 
 // The same for a batch planned with par_sub_bits: gpu == 1 entries as above, gpu == 2
 // entries also against their JpegParDesc and the scratch buffer (scratch_cap uint32
 // elements, kJpegParStateWords per sub-stream of sub_bits bits).
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false);
+                                bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false,
+                                bool allow_colorspace = false);
 
 // The gpu == 3 entries against the scan buffer (nscans JpegProgScan) and the table
 // buffer (ntabs JpegHuffTab) the progressive kernel will get: every image's scan

@@ -35,7 +35,7 @@ from .runtime.executor import HipExecutor, TorchExecutor
 from .runtime.jobstate import class_names
 
 _EXECUTORS: dict = {}
-# (device, directory, entropy_on, progressive, restart, sampling) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
+# (device, directory, entropy_on, progressive, restart, colorspace, sampling) -> GpuJpegSource: its decoded images stay resident across calls, keyed by
 # index only; after replacing files of a directory call drop_gpu_sources()
 _GPU_SOURCES: dict = {}
 _LOCK = threading.Lock()
@@ -66,7 +66,7 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
                  device: str | torch.device | None = None, batch: int | None = None, seed: int = 0,
                  data_seed: int = 1234, root: str = ".", decoder: str = "pil", entropy_on: str = "host",
                  progressive: str = "fallback", restart: str = "lane", topk: int = 1, weights=None,
-                 classes: str | None = None, sampling: str = "fallback"):
+                 classes: str | None = None, sampling: str = "fallback", colorspace: str = "ycbcr"):
     """Classify images ``start_image..end_image`` (inclusive).  Returns
     ``(list[(image_name, category, prob)], elapsed_seconds)`` like the reference.
     ``topk`` > 1 (at most 16) returns ``(image_name, (cat_1..cat_k),
@@ -91,7 +91,12 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
     per lane instead of on one lane; the default is ``"lane"``.
     ``sampling="native"`` (with ``decoder="gpu"``) decodes 4:4:0 and 4:1:1
     JPEG files natively instead of handing them to Pillow; the default is
-    ``"fallback"``."""
+    ``"fallback"``.
+    ``colorspace="auto"`` (with ``decoder="gpu"``) reads the colour model of a
+    JPEG file from its JFIF / Adobe markers and component ids as libjpeg does
+    and decodes RGB-coded, CMYK and YCCK files natively.  Under the default
+    ``"ycbcr"`` CMYK / YCCK files go to Pillow and an RGB-coded
+    three-component file is decoded as YCbCr, which gives wrong colours."""
     if decoder not in ("pil", "gpu"):
         raise ValueError(f"decoder must be 'pil' or 'gpu', not {decoder!r}")
     if entropy_on not in ("host", "gpu", "gpu_parallel"):
@@ -102,6 +107,8 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         raise ValueError(f"restart must be 'lane' or 'intervals', not {restart!r}")
     if sampling not in ("fallback", "native"):
         raise ValueError(f"sampling must be 'fallback' or 'native', not {sampling!r}")
+    if colorspace not in ("ycbcr", "auto"):
+        raise ValueError(f"colorspace must be 'ycbcr' or 'auto', not {colorspace!r}")
     if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= 16:
         raise ValueError(f"topk must be an integer in [1, 16], not {topk!r}")
     t0 = time.time()
@@ -115,11 +122,11 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
         src = SyntheticSource(data_seed, device)
     elif decoder == "gpu":
         with _LOCK:
-            key = (str(device), os.path.abspath(d), entropy_on, progressive, restart, sampling)
+            key = (str(device), os.path.abspath(d), entropy_on, progressive, restart, colorspace, sampling)
             src = _GPU_SOURCES.get(key)
             if src is None:
                 src = _GPU_SOURCES[key] = GpuJpegSource(device, root=d, entropy_on=entropy_on, progressive=progressive,
-                                                              restart=restart, sampling=sampling)
+                                                              restart=restart, sampling=sampling, colorspace=colorspace)
     else:
         src = JpegSource(device, root=d)
     names = class_names(path=classes)
@@ -158,6 +165,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "restart interval per lane")
     ap.add_argument("--sampling", default="fallback", choices=["fallback", "native"],
                     help="with --decoder gpu: 4:4:0 and 4:1:1 JPEG files through Pillow, or decoded natively")
+    ap.add_argument("--colorspace", default="ycbcr", choices=["ycbcr", "auto"],
+                    help="with --decoder gpu: every three-component JPEG file taken for YCbCr and CMYK / YCCK files "
+                         "through Pillow, or the colour model read from the file and RGB / CMYK / YCCK decoded natively")
     ap.add_argument("--topk", type=int, default=1, help="categories per image, most probable first (1..16)")
     ap.add_argument("--weights", default=None,
                     help="checkpoint file for the model (.safetensors or a torch.save'd state dict); default random-init")
@@ -169,7 +179,8 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     res, dt = deeplearning(a.dir or a.model, a.model, a.start, a.end, device=a.device, batch=a.batch,
                            decoder=a.decoder, entropy_on=a.entropy, progressive=a.progressive, restart=a.restart,
-                           topk=a.topk, weights=a.weights, classes=a.classes, sampling=a.sampling)
+                           topk=a.topk, weights=a.weights, classes=a.classes, sampling=a.sampling,
+                           colorspace=a.colorspace)
     for r in res:
         print(json.dumps(r))
     print(f"{len(res)} images in {dt:.3f} s ({len(res) / max(dt, 1e-9):.1f} img/s)", file=sys.stderr)

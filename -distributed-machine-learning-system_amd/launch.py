@@ -79,7 +79,7 @@ def run_node(a) -> int:
         # real files: `put` test_<i>.JPEG into SDFS, then `inference <start> <end> <model>`
         node.source = GpuJpegSource(sdfs=node.sdfs, device=dev, entropy_on=a.jpeg_entropy,
                                     progressive=a.jpeg_progressive, restart=a.jpeg_restart,
-                                    sampling=a.jpeg_sampling)
+                                    sampling=a.jpeg_sampling, colorspace=a.jpeg_colorspace)
     else:
         node.source = (SdfsSource(node.sdfs, dev, peer_copy=cfg.sdfs_peer_copy) if a.source == "sdfs"
                        else SyntheticSource(cfg.data_seed, dev))
@@ -105,7 +105,8 @@ def run_cluster(a) -> int:
     procs = []
     base = [sys.executable, "-m", "idunno.launch", "node", "--executor", a.executor, "--source", a.source,
             "--jpeg-entropy", a.jpeg_entropy, "--jpeg-progressive", a.jpeg_progressive,
-            "--jpeg-restart", a.jpeg_restart, "--jpeg-sampling", a.jpeg_sampling]
+            "--jpeg-restart", a.jpeg_restart, "--jpeg-sampling", a.jpeg_sampling,
+            "--jpeg-colorspace", a.jpeg_colorspace]
     for flag, v in (("--config", a.config), ("--nodes", cfg.num_nodes), ("--base-port", cfg.base_port),
                     ("--store-root", cfg.store_root), ("--log-dir", a.log_dir)):
         if v is not None:
@@ -162,6 +163,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "restart interval per lane")
     ap.add_argument("--jpeg-sampling", default="fallback", choices=["fallback", "native"],
                     help="--source jpeg: 4:4:0 and 4:1:1 files through Pillow, or decoded natively")
+    ap.add_argument("--jpeg-colorspace", default="ycbcr", choices=["ycbcr", "auto"],
+                    help="--source jpeg: every three-component file taken for YCbCr and CMYK / YCCK through Pillow, or "
+                         "the colour model read from the file and RGB / CMYK / YCCK decoded natively")
     ap.add_argument("--weights", action="append", default=None, metavar="MODEL=PATH",
                     help="checkpoint file for a model (repeatable); every node reads the same file")
     ap.add_argument("--shell", action="store_true")

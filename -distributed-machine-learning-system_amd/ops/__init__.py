@@ -357,21 +357,36 @@ def jpeg_parse(data: bytes, native_progressive: bool = False, native_sampling: b
     """Markers of a JPEG up to SOS: (status, reason, header dict or None);
     status 0 = a baseline file the native decoder takes.  With
     ``native_progressive`` a progressive file is walked up to EOI and taken too;
-    with ``native_sampling`` a 4:4:0 or 4:1:1 frame is taken as ``mode`` 3 or 4."""
+    with ``native_sampling`` a 4:4:0 or 4:1:1 frame is taken as ``mode`` 3 or 4.
+    The header's ``colorspace`` is 0 here: every three-component file counts as
+    YCbCr, an RGB-coded one included (``jpeg_parse_colorspace`` reads it)."""
     return load().jpeg_parse(data, bool(native_progressive), bool(native_sampling))
 
 
-def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False, native_sampling: bool = False):
+def jpeg_parse_colorspace(data: bytes, native_progressive: bool = False, native_sampling: bool = False,
+                          native_colorspace: bool = True):
+    """``jpeg_parse`` with the extension's fourth argument (``jpeg_parse`` itself keeps
+    its three parameters, which tests/test_jpeg_sampling_cpu.py pins): with
+    ``native_colorspace`` the header's ``colorspace`` says what the JFIF /
+    Adobe markers and the component ids make of the samples (0 YCbCr or grey,
+    1 RGB, 2 CMYK, 3 YCCK) and a four-component frame sampled 1x1 is taken."""
+    return load().jpeg_parse(data, bool(native_progressive), bool(native_sampling), bool(native_colorspace))
+
+
+def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False, native_sampling: bool = False,
+                       native_colorspace: bool = False):
     """Huffman-decode a list of ``bytes | None`` on ``threads`` native threads
     (GIL released): (status per entry, headers, int16 coefficients on the
-    host, first coefficient of each entry or -1)."""
-    return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive), bool(native_sampling))
+    host, first coefficient of each entry or -1).  ``native_colorspace``: as
+    for ``jpeg_parse``; 1x1 CMYK / YCCK files are decoded too."""
+    return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive), bool(native_sampling),
+                                     bool(native_colorspace))
 
 
 # the sub-stream kernel's constants, then the progressive decoder's: the scan cap of one file
-# (csrc/jpeg_huff_prog.h) and where a header row keeps its ``progressive`` and ``mode`` ints
+# (csrc/jpeg_huff_prog.h) and where a header row keeps its ``progressive``, ``mode`` and ``colorspace`` ints
 _JPEG_PAR_CONSTANTS = ("JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS", "JPEG_PROG_MAX_SCANS",
-                       "JPEG_HEADER_PROGRESSIVE_OFFSET", "JPEG_HEADER_MODE_OFFSET")
+                       "JPEG_HEADER_PROGRESSIVE_OFFSET", "JPEG_HEADER_MODE_OFFSET", "JPEG_HEADER_COLORSPACE_OFFSET")
 
 
 def __getattr__(name: str):
@@ -383,7 +398,7 @@ def __getattr__(name: str):
 
 
 def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = False,
-                   restart_intervals: bool = False, native_sampling: bool = False):
+                   restart_intervals: bool = False, native_sampling: bool = False, native_colorspace: bool = False):
     """Parse a list of ``bytes | None`` and pack the accepted entries for the
     device entropy stage (GIL released): a ``JpegHuffPacked`` with the parse
     ``status``, ``hdr`` and ``offs`` of ``jpeg_entropy_batch`` and the packed
@@ -397,9 +412,13 @@ def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = Fal
     MCU, interval index) for the interval kernel, which the same two calls
     launch; ``n_lane`` keeps counting the entries of the one-lane kernel.
     ``native_sampling``: 4:4:0 and 4:1:1 files are accepted (modes 3 and 4 in
-    their header rows) and packed like every other file of their kind."""
+    their header rows) and packed like every other file of their kind.
+    ``native_colorspace``: the header rows' ``colorspace`` is classified and
+    1x1 CMYK / YCCK files are accepted, always for the one-lane kernel or, when
+    progressive, the progressive one; RGB-coded files are packed like their
+    YCbCr twins.  The batch remembers the flag in ``native_colorspace``."""
     return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive), bool(restart_intervals),
-                                 bool(native_sampling))
+                                 bool(native_sampling), bool(native_colorspace))
 
 
 def jpeg_entropy_zero(coefs):

@@ -650,7 +650,12 @@ class GpuJpegSource:
 
     ``sampling="native"`` (opt-in, default ``"fallback"``) decodes 4:4:0 and
     4:1:1 files natively in whichever form ``entropy_on`` names instead of
-    handing them to ``load_image_u8``; ``sampling_images`` counts them."""
+    handing them to ``load_image_u8``; ``sampling_images`` counts them.
+
+    ``colorspace="auto"`` (opt-in, default ``"ycbcr"``) reads each file's colour
+    model as libjpeg does and decodes RGB-coded, CMYK and YCCK files natively;
+    ``colorspace_images`` counts them.  Under the default CMYK / YCCK files go
+    to ``load_image_u8`` and an RGB-coded file is decoded as YCbCr."""
 
     CHUNK = 256          # images per decode_batch call (bounds the coefficient buffers: ~0.6 MB per 500x375 image)
     # entropy_on="gpu": one lane decodes one image, so the entropy kernel's throughput is the chunk
@@ -661,7 +666,8 @@ class GpuJpegSource:
 
     def __init__(self, device, root: str | None = None, sdfs=None, prefix: str = "", cache_bytes: int = 16 << 30,
                  threads: int = 8, resize: int = 256, crop: int = HW, entropy_on: str = "host",
-                 progressive: str = "fallback", restart: str = "lane", sampling: str = "fallback"):
+                 progressive: str = "fallback", restart: str = "lane", sampling: str = "fallback",
+                 colorspace: str = "ycbcr"):
         from concurrent.futures import ThreadPoolExecutor
 
         from . import jpeg
@@ -670,6 +676,7 @@ class GpuJpegSource:
         self.progressive = jpeg._check_progressive(progressive)
         self.restart = jpeg._check_restart(restart)
         self.sampling = jpeg._check_sampling(sampling)
+        self.colorspace = jpeg._check_colorspace(colorspace)
         self.device = torch.device(device)
         self.root, self.sdfs, self.prefix = root, sdfs, prefix
         self.cache_bytes = int(cache_bytes)
@@ -684,6 +691,7 @@ class GpuJpegSource:
         self.progressive_images = 0  # of which progressive files decoded natively (progressive="native")
         self.restart_images = 0     # of which decoded one restart interval per lane (restart="intervals")
         self.sampling_images = 0    # of which 4:4:0 / 4:1:1 files decoded natively (sampling="native")
+        self.colorspace_images = 0  # of which RGB / CMYK / YCCK files decoded natively (colorspace="auto")
         self.cache_hits = 0         # images served from HBM without a decode
         self.fallback_reasons: dict[int, str] = {}
         self.seconds = {"entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0}
@@ -735,7 +743,7 @@ class GpuJpegSource:
             # previous chunk's host -> HBM copy and kernels
             datas = list(self.readers.map(self._read, part))
             return datas, (jpeg.entropy_batch(datas, self.threads, self.entropy_on, self.progressive, self.restart,
-                                              self.sampling) if gpu else None)
+                                              self.sampling, self.colorspace) if gpu else None)
 
         got, absent = {}, set()
         chunk = self.CHUNK
@@ -753,7 +761,7 @@ class GpuJpegSource:
                 nxt = self._front.submit(front, parts[k + 1])
             imgs, info = jpeg.decode_batch(datas, self.device, self.resize, self.crop, self.threads, self.stager,
                                            entropy=ent, entropy_on=self.entropy_on, progressive=self.progressive,
-                                           restart=self.restart, sampling=self.sampling)
+                                           restart=self.restart, sampling=self.sampling, colorspace=self.colorspace)
             for name in self.seconds:
                 self.seconds[name] += info[name]
             for j, reason in info["fallbacks"]:
@@ -762,6 +770,7 @@ class GpuJpegSource:
             self.progressive_images += info["progressive_images"]
             self.restart_images += info["restart_images"]
             self.sampling_images += info["sampling_images"]
+            self.colorspace_images += info["colorspace_images"]
             for j, i in enumerate(part):
                 if datas[j] is None:
                     self.missing.append(i)

@@ -45,11 +45,26 @@ stage upsamples mode 3 with libjpeg's vertical triangle filter and mode 4 by
 replication, as libjpeg-turbo does, on planes that an fp64 IDCT pass
 (jpeg_idct_exact_kernel) has rewritten so that near-ties round as the model's.
 
+``colorspace="auto"`` (opt-in, default ``"ycbcr"``) reads the colour model of a
+file as libjpeg does: a three-component file with a JFIF APP0 is YCbCr; else
+an Adobe APP14 decides (transform 0: RGB, else YCbCr); else the component
+ids (``R``, ``G``, ``B``: RGB, anything else: YCbCr).  A four-component file
+whose components are all sampled 1x1 is CMYK (no Adobe segment, or transform
+0) or YCCK (transform 2).  RGB-coded files are decoded wherever their YCbCr
+twins are; four-component files take the one-lane kernel (the progressive
+kernel when progressive) in both device forms.  The colour stage of the
+resize kernel hands RGB planes on as they are and converts CMYK / YCCK with
+Pillow's integer formula, on planes the fp64 IDCT pass has rewritten.  Under
+the default ``"ycbcr"`` nothing of this is read: a four-component file is a
+``"components"`` fallback, and an RGB-coded three-component file is decoded
+as YCbCr, which gives wrong colours without a fallback being reported.
+
 The chain reproduces what ``load_image_u8`` gets from libjpeg-turbo + Pillow
 (fancy upsampling, YCbCr -> RGB, BILINEAR resize in two rounded passes, centre
 crop) to within the tolerances of tests/test_jpeg_gpu.py.  Files the native
 decoder does not take (progressive unless ``progressive="native"``,
-non-interleaved baseline, arithmetic, 12-bit, CMYK, 4:4:0 / 4:1:1 unless
+non-interleaved baseline, arithmetic, 12-bit, CMYK / YCCK unless
+``colorspace="auto"``, 4:4:0 / 4:1:1 unless
 ``sampling="native"``, any other odd sampling,
 corrupt, not a JPEG at all) are decoded by ``load_image_u8`` on the host and
 reported in ``info["fallbacks"]``; on a CPU device every image takes that
@@ -101,29 +116,46 @@ def _check_sampling(sampling: str) -> str:
     return sampling
 
 
-def parse(data: bytes, progressive: str = "fallback", sampling: str = "fallback"):
+COLORSPACE = ("ycbcr", "auto")
+# header["colorspace"]: what the samples of a file are
+CS_YCBCR, CS_RGB, CS_CMYK, CS_YCCK = 0, 1, 2, 3
+
+
+def _check_colorspace(colorspace: str) -> str:
+    if colorspace not in COLORSPACE:
+        raise ValueError(f"colorspace must be one of {COLORSPACE}, not {colorspace!r}")
+    return colorspace
+
+
+def parse(data: bytes, progressive: str = "fallback", sampling: str = "fallback", colorspace: str = "ycbcr"):
     """Header of a JPEG the native decoder takes (dict: W, H, ncomp, mode,
-    comp[i] = h, v, bw, bh, coef_off, q, progressive, nscans), or the reason
-    (str) it does not.  A progressive file is ``"progressive"`` unless
-    ``progressive="native"``; a 4:4:0 or 4:1:1 file is ``"sampling"`` unless
-    ``sampling="native"`` (then ``mode`` 3 or 4)."""
+    comp[i] = h, v, bw, bh, coef_off, q, progressive, nscans, colorspace), or
+    the reason (str) it does not.  A progressive file is ``"progressive"``
+    unless ``progressive="native"``; a 4:4:0 or 4:1:1 file is ``"sampling"``
+    unless ``sampling="native"`` (then ``mode`` 3 or 4).  With
+    ``colorspace="auto"`` the header's ``colorspace`` is 0 (YCbCr or grey), 1
+    (RGB), 2 (CMYK) or 3 (YCCK) and a four-component file sampled 1x1 is taken;
+    with the default ``"ycbcr"`` it is always 0, a four-component file is
+    ``"components"`` and an RGB-coded file is decoded as YCbCr."""
     native = _check_progressive(progressive) == "native"
     samp = _check_sampling(sampling) == "native"
-    st, reason, hdr = _C().jpeg_parse(bytes(data), native, samp)
+    color = _check_colorspace(colorspace) == "auto"
+    st, reason, hdr = _C().jpeg_parse_colorspace(bytes(data), native, samp, color)
     return hdr if st == 0 else reason
 
 
-def entropy_decode(data: bytes, progressive: str = "fallback", sampling: str = "fallback"):
+def entropy_decode(data: bytes, progressive: str = "fallback", sampling: str = "fallback", colorspace: str = "ycbcr"):
     """(header, int16 coefficients) of one image by the native host decoder, or
-    the reason (str) it was refused."""
+    the reason (str) it was refused.  ``colorspace``: as for ``parse``."""
     native = _check_progressive(progressive) == "native"
     samp = _check_sampling(sampling) == "native"
+    color = _check_colorspace(colorspace) == "auto"
     data = bytes(data)
-    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native, samp)
+    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native, samp, color)
     if status[0] != 0:
-        st, reason, _ = _C().jpeg_parse(data, native, samp)
+        st, reason, _ = _C().jpeg_parse_colorspace(data, native, samp, color)
         return reason if st != 0 else "corrupt"
-    return parse(data, progressive, sampling), coefs.numpy()
+    return parse(data, progressive, sampling, colorspace), coefs.numpy()
 
 
 # ---- float64 model of the GPU chain ------------------------------------------------
@@ -179,11 +211,22 @@ def _upsample_h1v2(p: np.ndarray) -> np.ndarray:
     return out
 
 
+def _muldiv255(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Pillow's MULDIV255 on integer arrays: a * b / 255 rounded half up."""
+    t = a * b + 128
+    return ((t >> 8) + t) >> 8
+
+
 def reference_backend(header: dict, coeffs: np.ndarray) -> np.ndarray:
     """Full-resolution RGB uint8 [H, W, 3] from a header and its coefficients:
     exact IDCT in float64, planes cut to their downsampled size, libjpeg's
     fancy upsampling (mode 4, h4v1: replication, libjpeg has no filter for
-    it), colour conversion rounded half up."""
+    it), colour conversion rounded half up.  ``header["colorspace"]`` picks
+    the colour stage: YCbCr (0; a header parsed under the default always says
+    so), RGB (1: the upsampled planes as they are), CMYK (2) and YCCK (3) as
+    Pillow converts them, ``nk - MULDIV255(c, nk)`` with ``nk`` the fourth
+    plane and ``c`` 255 minus a plane (CMYK) or the R', G', B' of planes 0..2
+    (YCCK), in integers."""
     W, H = header["W"], header["H"]
     hmax, vmax = header["hmax"], header["vmax"]
     m = _idct_matrix()
@@ -200,10 +243,24 @@ def reference_backend(header: dict, coeffs: np.ndarray) -> np.ndarray:
         return np.repeat(y[:, :, None], 3, 2).astype(np.uint8)
     up = {0: lambda p: p, 1: _upsample_h2v1, 2: _upsample_h2v2, 3: _upsample_h1v2,
           4: lambda p: np.repeat(p, 4, 1)}[header["mode"]]
-    cb = up(planes[1])[:H, :W].astype(np.float64) - 128.0
-    cr = up(planes[2])[:H, :W].astype(np.float64) - 128.0
-    rgb = np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], 2)
-    return _round_u8(rgb).astype(np.uint8)
+    cs = header.get("colorspace", CS_YCBCR)
+    if cs == CS_RGB and header["mode"] in (1, 2) and planes[1].shape[1] <= 2:
+        # libjpeg filters a half-width plane only when it is more than two samples wide, else it
+        # replicates; a YCbCr pixel dilutes the difference, an RGB plane is the pixel
+        up = lambda p, v=header["mode"]: np.repeat(np.repeat(p, 2, 1), v, 0)
+    p1, p2 = up(planes[1])[:H, :W], up(planes[2])[:H, :W]
+    if cs == CS_RGB:
+        return np.stack([y, p1, p2], 2).astype(np.uint8)
+    if cs == CS_CMYK:
+        nk = planes[3].astype(np.int64)
+        return np.stack([nk - _muldiv255(255 - p.astype(np.int64), nk) for p in (y, p1, p2)], 2).astype(np.uint8)
+    cb = p1.astype(np.float64) - 128.0
+    cr = p2.astype(np.float64) - 128.0
+    rgb = _round_u8(np.stack([y + 1.402 * cr, y - 0.344136 * cb - 0.714136 * cr, y + 1.772 * cb], 2))
+    if cs == CS_YCCK:
+        nk = planes[3].astype(np.int64)[:, :, None]
+        rgb = nk - _muldiv255(rgb.astype(np.int64), nk)
+    return rgb.astype(np.uint8)
 
 
 def _bilinear_weights(n_in: int, n_out: int) -> np.ndarray:
@@ -267,10 +324,10 @@ _DEVICE_FORMS = ("gpu", "gpu_parallel")
 _UNSYNCED = 100           # kJpegHuffUnsynced: the sub-stream kernel's rounds hit their cap (device-only status)
 
 
-def _refusal(C, data: bytes, status: int, native: bool = False, samp: bool = False) -> str:
-    """Why an entry is a fallback: the parse's reason (in the progressive and sampling modes
-    the batch was decoded in), else what the entropy stage said."""
-    st, reason, _ = C.jpeg_parse(data, native, samp)
+def _refusal(C, data: bytes, status: int, native: bool = False, samp: bool = False, color: bool = False) -> str:
+    """Why an entry is a fallback: the parse's reason (in the progressive, sampling and colorspace
+    modes the batch was decoded in), else what the entropy stage said."""
+    st, reason, _ = C.jpeg_parse_colorspace(data, native, samp, color)
     if st != 0:
         return reason
     return "unsynced" if status == _UNSYNCED else "corrupt"
@@ -283,7 +340,7 @@ def _check_entropy_on(entropy_on: str) -> str:
 
 
 def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback",
-                  restart: str = "lane", sampling: str = "fallback"):
+                  restart: str = "lane", sampling: str = "fallback", colorspace: str = "ycbcr"):
     """The host half of ``decode_batch`` for a GPU device: the native Huffman
     decode of a list of ``bytes | None`` on ``threads`` threads (the GIL is
     released, so a caller may run it under the previous batch's copy and
@@ -293,19 +350,22 @@ def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive
     files in either form; ``restart="intervals"`` packs one work item per
     restart interval for the interval kernel in the two device forms (the host
     form is unchanged by it); ``sampling="native"`` takes 4:4:0 and 4:1:1 files
-    in every form.  Returns what ``decode_batch(..., entropy=)`` takes; the
+    in every form; ``colorspace="auto"`` classifies RGB-coded files and takes
+    1x1 CMYK / YCCK files in every form (under the default every
+    three-component file counts as YCbCr, an RGB-coded one included).  Returns what ``decode_batch(..., entropy=)`` takes; the
     result remembers the options."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
     intervals = _check_restart(restart) == "intervals"
     samp = _check_sampling(sampling) == "native"
+    color = _check_colorspace(colorspace) == "auto"
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
     if entropy_on in _DEVICE_FORMS:
-        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp)
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp, color)
         return entropy_on, datas, packed, time.perf_counter() - t0
-    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native, samp)
-    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive, sampling
+    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native, samp, color)
+    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive, sampling, colorspace
 
 
 def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
@@ -340,7 +400,7 @@ def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
 
 
 def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 8, progressive: str = "fallback",
-                  restart: str = "lane", sampling: str = "fallback"):
+                  restart: str = "lane", sampling: str = "fallback", colorspace: str = "ycbcr"):
     """Debug helper: the entropy stage alone.  ``(status, offs, coefs)``: one
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
@@ -348,22 +408,25 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
     GPU ``device``, from the entropy kernels.  ``progressive="native"``:
     progressive files are decoded too, in every form.  ``restart="intervals"``:
     the device forms decode restart-interval files one interval per lane.
-    ``sampling="native"``: 4:4:0 and 4:1:1 files are decoded too, in every form."""
+    ``sampling="native"``: 4:4:0 and 4:1:1 files are decoded too, in every form.
+    ``colorspace="auto"``: 1x1 CMYK / YCCK files are decoded too, in every form
+    (on the one-lane or the progressive kernel in the device forms)."""
     _check_entropy_on(entropy_on)
     native = _check_progressive(progressive) == "native"
     intervals = _check_restart(restart) == "intervals"
     samp = _check_sampling(sampling) == "native"
+    color = _check_colorspace(colorspace) == "auto"
     C = _C()
     datas = [None if d is None else bytes(d) for d in datas]
     if entropy_on == "host":
-        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native, samp)
+        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native, samp, color)
         return list(status), list(offs), coefs
     device = torch.device(device)
     if device.type != "cuda":
         raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp)
+    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp, color)
     status = list(packed.status)
     coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
     if packed.n_gpu:
@@ -380,7 +443,8 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
 
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
                  stager: HbmStager | None = None, entropy=None, entropy_on: str = "host",
-                 progressive: str = "fallback", restart: str = "lane", sampling: str = "fallback"):
+                 progressive: str = "fallback", restart: str = "lane", sampling: str = "fallback",
+                 colorspace: str = "ycbcr"):
     """Decode a list of ``bytes | None`` into a uint8 tensor [B, crop, crop, 3] on
     ``device`` (``None`` entries: zero images).  With ``resize=None`` nothing is
     resized or cropped and the result is a list of [H, W, 3] tensors (``None``
@@ -449,11 +513,34 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     mode in effect (when ``entropy`` was prepared, the one it was prepared in;
     on a CPU device the one asked for, and nothing native runs),
     ``info["sampling_images"]`` counts the mode-3 and mode-4 images decoded
-    natively and not flagged."""
+    natively and not flagged.
+
+    ``colorspace="auto"`` (default ``"ycbcr"``) reads each file's colour model
+    as libjpeg does.  Three components: YCbCr when the file has a JFIF APP0;
+    else RGB for an Adobe APP14 with transform 0 and YCbCr for any other
+    transform; else RGB for the component ids ``R``, ``G``, ``B`` and YCbCr
+    otherwise.  Four components, all sampled 1x1, baseline or (with
+    ``progressive="native"``) progressive, with or without restart markers:
+    CMYK without an Adobe segment or with transform 0, YCCK with transform 2;
+    any other transform stays a ``"components"`` fallback and any other
+    four-component sampling is a ``"sampling"`` one.  RGB-coded files go
+    through whichever entropy kernel their YCbCr twins take; four-component
+    files take the one-lane kernel (or the progressive one) under ``"gpu"``,
+    ``"gpu_parallel"`` and ``restart="intervals"`` alike.  The resize kernel
+    hands RGB planes on as they are (planes 1 and 2 upsampled like chroma) and
+    converts CMYK / YCCK as Pillow's ``convert("RGB")`` does, in integers.
+    Under the default ``"ycbcr"`` every four-component file is a
+    ``"components"`` fallback and an RGB-coded three-component file is decoded
+    as YCbCr: its colours are wrong and no fallback is reported.
+    ``info["colorspace"]`` names the mode in effect (when ``entropy`` was
+    prepared, the one it was prepared in; on a CPU device the one asked for,
+    and nothing native runs), ``info["colorspace_images"]`` counts the RGB /
+    CMYK / YCCK images decoded natively and not flagged."""
     _check_entropy_on(entropy_on)
     _check_progressive(progressive)
     _check_restart(restart)
     _check_sampling(sampling)
+    _check_colorspace(colorspace)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
@@ -468,13 +555,17 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         if on_gpu:
             restart = "intervals" if entropy[2].restart_intervals else "lane"
             sampling = "native" if entropy[2].native_sampling else "fallback"
+            colorspace = "auto" if entropy[2].native_colorspace else "ycbcr"
         else:
             sampling = entropy[7]
+            colorspace = entropy[8]
     native = progressive == "native"
     samp = sampling == "native"
+    color = colorspace == "auto"
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
             "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0,
-            "restart": restart, "restart_images": 0, "sampling": sampling, "sampling_images": 0}
+            "restart": restart, "restart_images": 0, "sampling": sampling, "sampling_images": 0,
+            "colorspace": colorspace, "colorspace_images": 0}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -494,12 +585,13 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     packed = None
     if on_gpu:
         _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form,
-                                                                                         progressive, restart, sampling)
+                                                                                         progressive, restart, sampling,
+                                                                                         colorspace)
         status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
     else:
         _, status, hdr, coefs, offs, info["entropy_s"] = (entropy if entropy is not None else
                                                           entropy_batch(datas, threads, "host", progressive,
-                                                                        sampling=sampling))[:6]
+                                                                        sampling=sampling, colorspace=colorspace))[:6]
         status = list(status)
         coef_elems = coefs.numel()
     geom = None
@@ -563,7 +655,7 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 imgs.append(None)
                 continue
             if status[i] != 0:
-                info["fallbacks"].append((i, _refusal(C, d, status[i], native, samp)))
+                info["fallbacks"].append((i, _refusal(C, d, status[i], native, samp, color)))
                 t = torch.from_numpy(host(d).copy()).to(device)
                 if full:
                     imgs.append(t)
@@ -579,6 +671,9 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
         if samp and n:
             mode = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_MODE_OFFSET // 4]
             info["sampling_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and mode[i] >= 3)
+        if color and n:
+            cs = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_COLORSPACE_OFFSET // 4]
+            info["colorspace_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and cs[i] != 0)
         # the result is complete when it is returned, whatever the batch held (the zero fill and
         # the fallbacks' copies too): a holder may hand it to a consumer on any other stream
         cur.synchronize()
