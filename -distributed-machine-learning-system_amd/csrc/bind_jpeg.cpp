@@ -43,16 +43,32 @@ static void bytes_span(const py::handle& o, const uint8_t** p, size_t* n) {
   *n = (size_t)len;
 }
 
+// A list of bytes / None as pointers and lengths: nullptr / 0 for None and for empty bytes.
+static void bytes_list(const py::list& datas, std::vector<const uint8_t*>* ptr, std::vector<size_t>* len) {
+  const size_t n = datas.size();
+  ptr->assign(n, nullptr);
+  len->assign(n, 0);
+  for (size_t i = 0; i < n; ++i) {
+    py::handle o = datas[i];
+    if (!o.is_none()) bytes_span(o, &(*ptr)[i], &(*len)[i]);
+    if ((*len)[i] == 0) (*ptr)[i] = nullptr;
+  }
+}
+
+// The flags of the Python functions below are the members of JpegOptions (runtime/jpeg_entropy.h),
+// which says what each admits; the struct is built here and nowhere else.
+
 // (status, reason, header dict or None)
-// native_progressive: a progressive file of a supported layout is walked to EOI and accepted
-// native_sampling: 4:4:0 and 4:1:1 frames are accepted as modes 3 and 4
-// native_colorspace: the header's colorspace is classified (else 0) and 1x1 CMYK / YCCK frames are accepted
 py::tuple jpeg_parse(py::bytes data, bool native_progressive, bool native_sampling, bool native_colorspace) {
+  JpegOptions opt;
+  opt.native_progressive = native_progressive;
+  opt.native_sampling = native_sampling;
+  opt.native_colorspace = native_colorspace;
   const uint8_t* p;
   size_t n;
   bytes_span(data, &p, &n);
   JpegHeader h;
-  const int st = jpeg_parse_header(n ? p : nullptr, n, &h, native_progressive, nullptr, native_sampling, native_colorspace);
+  const int st = jpeg_parse_header(n ? p : nullptr, n, &h, opt);
   return py::make_tuple(st, jpeg_status_name(st), st == JPEG_OK ? py::object(jpeg_header_dict(h)) : py::none());
 }
 
@@ -60,20 +76,17 @@ py::tuple jpeg_parse(py::bytes data, bool native_progressive, bool native_sampli
 // released.  Returns (status per entry, headers uint8 [n, sizeof(JpegHeader)],
 // coefficients int16 [total] on the host, first coefficient of each entry or -1).
 // Only entries whose header parses get room in the coefficient buffer.
-// native_progressive: progressive files are decoded too (the core of jpeg_huff_prog.h).
-// native_sampling: 4:4:0 and 4:1:1 files are decoded too (modes 3 and 4).
-// native_colorspace: RGB-coded files are classified and 1x1 CMYK / YCCK files are decoded too.
 py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progressive, bool native_sampling,
                              bool native_colorspace) {
+  JpegOptions opt;
+  opt.native_progressive = native_progressive;
+  opt.native_sampling = native_sampling;
+  opt.native_colorspace = native_colorspace;
   const int n = (int)datas.size();
   TORCH_CHECK(threads >= 1 && threads <= 256, "threads out of range");
-  std::vector<const uint8_t*> ptr(n, nullptr);
-  std::vector<size_t> len(n, 0), cap(n, 0);
-  for (int i = 0; i < n; ++i) {
-    py::handle o = datas[i];
-    if (!o.is_none()) bytes_span(o, &ptr[i], &len[i]);
-    if (ptr[i] != nullptr && len[i] == 0) ptr[i] = nullptr;
-  }
+  std::vector<const uint8_t*> ptr;
+  std::vector<size_t> len, cap(n, 0);
+  bytes_list(datas, &ptr, &len);
   auto hdr = torch::zeros({n, (int64_t)sizeof(JpegHeader)}, torch::kUInt8);
   JpegHeader* hp = reinterpret_cast<JpegHeader*>(hdr.data_ptr());
   std::vector<int> status(n, JPEG_EMPTY);
@@ -85,8 +98,7 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progre
     py::gil_scoped_release nogil;
     for (int i = 0; i < n; ++i) {
       if (ptr[i] == nullptr) continue;
-      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i], native_progressive, nullptr, native_sampling,
-                                    native_colorspace);
+      status[i] = jpeg_parse_header(ptr[i], len[i], &hp[i], opt);
       if (status[i] != JPEG_OK) {
         ptr[i] = nullptr;                    // keeps its parse status: not decoded
         continue;
@@ -105,8 +117,7 @@ py::tuple jpeg_entropy_batch(py::list datas, int64_t threads, bool native_progre
     std::vector<int> st2(n, JPEG_EMPTY);
     std::vector<JpegHeader> h2((size_t)n);
     py::gil_scoped_release nogil;
-    jpeg_decode_batch(n, ptr.data(), len.data(), h2.data(), out.data(), cap.data(), st2.data(), (int)threads,
-                      native_progressive, native_sampling, native_colorspace);
+    jpeg_decode_batch(n, ptr.data(), len.data(), h2.data(), out.data(), cap.data(), st2.data(), (int)threads, opt);
     for (int i = 0; i < n; ++i)
       if (ptr[i] != nullptr) status[i] = st2[i];
   }
@@ -292,41 +303,32 @@ struct JpegHuffPacked {
   bool parallel = false;
   torch::Tensor par;
   int64_t n_par = 0, n_lane = 0, scratch_total = 0;
-  // packed with native_progressive: the progressive entries (gpu == 3) as JpegProgScan[nscans],
-  // JpegHuffTab[ntabs] and the int32 indices of those entries, for jpeg_entropy_prog_kernel
-  bool native_progressive = false;
+  // what the batch was packed with; the checks before a launch admit what it admits
+  JpegOptions opt;
+  // the progressive entries (gpu == 3) as JpegProgScan[nscans], JpegHuffTab[ntabs] and the int32 indices
+  // of those entries, for jpeg_entropy_prog_kernel
   torch::Tensor scans, tabs, prog_list;
   int64_t n_prog = 0, nscans = 0, ntabs = 0;
-  // packed with restart_intervals: the baseline entries with a restart interval whose markers the packer
-  // found (gpu == 4) as JpegRstItem[nitems], int32 [nitems, 4] = (entry, byte_begin, mcu_first, index),
-  // for jpeg_entropy_rst_kernel; n_lane keeps counting the gpu == 1 entries only
-  bool restart_intervals = false;
+  // the baseline entries with a restart interval whose markers the packer found (gpu == 4) as
+  // JpegRstItem[nitems], int32 [nitems, 4] = (entry, byte_begin, mcu_first, index), for
+  // jpeg_entropy_rst_kernel; n_lane keeps counting the gpu == 1 entries only
   torch::Tensor rst_items;
   int64_t n_rst = 0;
-  // packed with native_sampling: 4:4:0 and 4:1:1 files were accepted (modes 3 and 4 in hdr), laid out
-  // like every other file of their kind; the checks before a launch then admit their luma factors
-  bool native_sampling = false;
-  // packed with native_colorspace: the headers' colorspace is classified and 1x1 CMYK / YCCK files were
-  // accepted, on the one-lane or the progressive kernel; the checks before a launch then admit four components
-  bool native_colorspace = false;
 };
 
 // Parses a list of bytes / None and packs the accepted entries, GIL released.  parallel: lay the
 // entries without restart markers out for the sub-stream kernel (jpeg_entropy_gpu_parallel).
-// native_progressive: progressive files are accepted and laid out for the progressive kernel.
-// restart_intervals: baseline files with a restart interval get one work item per interval for the
-// interval kernel, in either layout.  native_sampling: 4:4:0 and 4:1:1 files are accepted.
-// native_colorspace: RGB-coded files are classified, 1x1 CMYK / YCCK files are accepted.
 std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bool native_progressive,
                                                bool restart_intervals, bool native_sampling, bool native_colorspace) {
+  JpegOptions opt;
+  opt.native_progressive = native_progressive;
+  opt.restart_intervals = restart_intervals;
+  opt.native_sampling = native_sampling;
+  opt.native_colorspace = native_colorspace;
   const int n = (int)datas.size();
-  std::vector<const uint8_t*> ptr(n, nullptr);
-  std::vector<size_t> len(n, 0);
-  for (int i = 0; i < n; ++i) {
-    py::handle o = datas[i];
-    if (!o.is_none()) bytes_span(o, &ptr[i], &len[i]);
-    if (ptr[i] != nullptr && len[i] == 0) ptr[i] = nullptr;
-  }
+  std::vector<const uint8_t*> ptr;
+  std::vector<size_t> len;
+  bytes_list(datas, &ptr, &len);
   auto pk = std::make_shared<JpegHuffPacked>();
   pk->n = n;
   pk->hdr = torch::zeros({n, (int64_t)sizeof(JpegHeader)}, torch::kUInt8);
@@ -335,15 +337,12 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   {
     py::gil_scoped_release nogil;
     jpeg_huff_plan(n, ptr.data(), len.data(), reinterpret_cast<JpegHeader*>(pk->hdr.data_ptr()), status.data(), &b,
-                   parallel ? kJpegParSubBits : 0u, native_progressive, restart_intervals, native_sampling,
-                   native_colorspace);
+                   parallel ? kJpegParSubBits : 0u, opt);
   }
   const char* why = parallel ? jpeg_huff_par_check(b.desc.data(), b.par.data(), n, b.byte_total, (int64_t)b.sets.size(),
-                                                   b.coef_total, b.scratch_total, kJpegParSubBits, native_progressive,
-                                                   restart_intervals, native_sampling, native_colorspace)
-                             : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total,
-                                               native_progressive, restart_intervals, native_sampling, native_colorspace);
-  if (why == nullptr && native_progressive)
+                                                   b.coef_total, b.scratch_total, kJpegParSubBits, opt)
+                             : jpeg_huff_check(b.desc.data(), n, b.byte_total, (int64_t)b.sets.size(), b.coef_total, opt);
+  if (why == nullptr && opt.native_progressive)
     why = jpeg_huff_prog_check(b.desc.data(), n, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   if (why == nullptr) why = jpeg_huff_rst_check(b.desc.data(), n, b.rst_items.data(), (int64_t)b.rst_items.size());
   TORCH_CHECK(why == nullptr, "jpeg_huff_pack: bad descriptor: ", why ? why : "");
@@ -354,7 +353,7 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   pk->par = torch::empty({(int64_t)(b.par.size() * sizeof(JpegParDesc))}, torch::kUInt8);
   if (!b.par.empty()) std::memcpy(pk->par.data_ptr(), b.par.data(), b.par.size() * sizeof(JpegParDesc));
   pk->scratch_total = b.scratch_total;
-  pk->native_progressive = native_progressive;
+  pk->opt = opt;
   pk->nscans = (int64_t)b.scans.size();
   pk->ntabs = (int64_t)b.tabs.size();
   pk->scans = torch::empty({(int64_t)(b.scans.size() * sizeof(JpegProgScan))}, torch::kUInt8);
@@ -362,9 +361,6 @@ std::shared_ptr<JpegHuffPacked> jpeg_huff_pack(py::list datas, bool parallel, bo
   if (!b.scans.empty()) std::memcpy(pk->scans.data_ptr(), b.scans.data(), b.scans.size() * sizeof(JpegProgScan));
   if (!b.tabs.empty()) std::memcpy(pk->tabs.data_ptr(), b.tabs.data(), b.tabs.size() * sizeof(JpegHuffTab));
   static_assert(sizeof(JpegRstItem) == 4 * sizeof(int32_t), "an item is a row of four int32");
-  pk->restart_intervals = restart_intervals;
-  pk->native_sampling = native_sampling;
-  pk->native_colorspace = native_colorspace;
   pk->rst_items = torch::empty({(int64_t)b.rst_items.size(), 4}, torch::kInt32);
   if (!b.rst_items.empty())
     std::memcpy(pk->rst_items.data_ptr(), b.rst_items.data(), b.rst_items.size() * sizeof(JpegRstItem));
@@ -413,7 +409,7 @@ static void check_entropy_operands(const char* op, const std::shared_ptr<JpegHuf
 }
 
 // The progressive entries of a packed batch (gpu == 3), one lane each, into the same coefs / status on
-// the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with allow_prog.
+// the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with pk->opt.
 static void launch_progressive(const char* op, const std::shared_ptr<JpegHuffPacked>& pk, const torch::Tensor& bytes,
                                const torch::Tensor& dev_desc, torch::Tensor& coefs, torch::Tensor& status) {
   if (pk->n_prog == 0) return;
@@ -437,7 +433,7 @@ static void launch_progressive(const char* op, const std::shared_ptr<JpegHuffPac
 }
 
 // The restart-interval entries of a packed batch (gpu == 4), one lane per interval, into the same coefs /
-// status on the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with allow_rst.
+// status on the current stream; the caller has run jpeg_huff_check / jpeg_huff_par_check with pk->opt.
 // The kernel only raises the status of an entry one of whose intervals is refused (atomic max) and writes
 // nothing for an accepted one, so status must be zero on entry: runtime/jpeg.py _entropy_on_device
 // allocates it with torch.zeros, and no other kernel writes the status of a gpu == 4 entry.
@@ -457,29 +453,53 @@ static void launch_restart(const char* op, const std::shared_ptr<JpegHuffPacked>
   check_launch("jpeg_entropy_rst");
 }
 
+// Both entropy entry points: operand checks, every descriptor against these very buffers, descriptor
+// uploads, then the one-lane kernel, the sub-stream kernel (scratch != nullptr: a batch packed with
+// parallel = true), the interval kernel and the progressive kernel, each on its own entries, all into
+// the same coefs / status on the current stream.
+static void entropy_launch(const char* op, const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor& bytes,
+                           torch::Tensor& coefs, torch::Tensor& status, torch::Tensor* scratch) {
+  if (pk->n_gpu == 0) return;
+  check_entropy_operands(op, pk, bytes, coefs, status);
+  const auto* hd = reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr());
+  const char* why;
+  if (scratch != nullptr) {
+    check_operand(*scratch, "scratch", torch::kInt32, -1, bytes.device());
+    TORCH_CHECK(pk->par.numel() == pk->n * (int64_t)sizeof(JpegParDesc), op, ": packed batch changed");
+    why = jpeg_huff_par_check(hd, reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n, bytes.numel(),
+                              pk->nsets, coefs.numel(), scratch->numel(), kJpegParSubBits, pk->opt);
+  } else {
+    why = jpeg_huff_check(hd, (int)pk->n, bytes.numel(), pk->nsets, coefs.numel(), pk->opt);
+  }
+  TORCH_CHECK(why == nullptr, op, ": descriptor outside its buffer: ", why ? why : "");
+  auto dev_desc = pk->desc.to(bytes.device());
+  auto dev_sets = pk->sets.to(bytes.device());
+  torch::Tensor dev_par;                     // every upload before the first launch: none waits for a kernel
+  if (scratch != nullptr) dev_par = pk->par.to(bytes.device());
+  const auto* sp = reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr());
+  const auto* dp = reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr());
+  if (pk->n_lane) {
+    jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), sp, dp, coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
+                        (int)pk->n, cur_stream());
+    check_launch("jpeg_entropy");
+  }
+  if (scratch != nullptr && pk->n_par) {
+    jpeg_entropy_par_launch(bytes.data_ptr<uint8_t>(), sp, dp, reinterpret_cast<const JpegParDesc*>(dev_par.data_ptr()),
+                            coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
+                            reinterpret_cast<uint32_t*>(scratch->data_ptr<int>()), (int)pk->n, cur_stream());
+    check_launch("jpeg_entropy_par");
+  }
+  launch_restart(op, pk, bytes, dev_desc, dev_sets, coefs, status);
+  launch_progressive(op, pk, bytes, dev_desc, coefs, status);
+}
+
 // Decodes the packed batch into coefs (zeroed by the caller: jpeg_entropy_zero) on the current
-// stream; status is written for the accepted entries only (zero on entry: see launch_restart).  Every descriptor is checked against
-// these very buffers first.
+// stream; status is written for the accepted entries only (zero on entry: see launch_restart).
 void jpeg_entropy_gpu(const std::shared_ptr<JpegHuffPacked>& pk, torch::Tensor bytes, torch::Tensor coefs,
                       torch::Tensor status) {
   TORCH_CHECK(pk != nullptr, "no packed batch");
   TORCH_CHECK(!pk->parallel, "jpeg_entropy_gpu: the batch was packed for jpeg_entropy_gpu_parallel");
-  if (pk->n_gpu == 0) return;
-  check_entropy_operands("jpeg_entropy_gpu", pk, bytes, coefs, status);
-  const char* why = jpeg_huff_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()), (int)pk->n,
-                                    bytes.numel(), pk->nsets, coefs.numel(), pk->native_progressive,
-                                    pk->restart_intervals, pk->native_sampling, pk->native_colorspace);
-  TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu: descriptor outside its buffer: ", why ? why : "");
-  auto dev_desc = pk->desc.to(bytes.device());
-  auto dev_sets = pk->sets.to(bytes.device());
-  if (pk->n_lane) {
-    jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr()),
-                        reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr()), coefs.data_ptr<int16_t>(),
-                        status.data_ptr<int>(), (int)pk->n, cur_stream());
-    check_launch("jpeg_entropy");
-  }
-  launch_restart("jpeg_entropy_gpu", pk, bytes, dev_desc, dev_sets, coefs, status);
-  launch_progressive("jpeg_entropy_gpu", pk, bytes, dev_desc, coefs, status);
+  entropy_launch("jpeg_entropy_gpu", pk, bytes, coefs, status, nullptr);
 }
 
 // The same for a batch packed with parallel = true: the sub-stream kernel on the entries laid out
@@ -489,34 +509,7 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
                                torch::Tensor status, torch::Tensor scratch) {
   TORCH_CHECK(pk != nullptr, "no packed batch");
   TORCH_CHECK(pk->parallel, "jpeg_entropy_gpu_parallel: the batch was packed for jpeg_entropy_gpu");
-  if (pk->n_gpu == 0) return;
-  check_entropy_operands("jpeg_entropy_gpu_parallel", pk, bytes, coefs, status);
-  check_operand(scratch, "scratch", torch::kInt32, -1, bytes.device());
-  TORCH_CHECK(pk->par.numel() == pk->n * (int64_t)sizeof(JpegParDesc), "jpeg_entropy_gpu_parallel: packed batch changed");
-  const char* why = jpeg_huff_par_check(reinterpret_cast<const JpegHuffDesc*>(pk->desc.data_ptr()),
-                                        reinterpret_cast<const JpegParDesc*>(pk->par.data_ptr()), (int)pk->n,
-                                        bytes.numel(), pk->nsets, coefs.numel(), scratch.numel(), kJpegParSubBits,
-                                        pk->native_progressive, pk->restart_intervals, pk->native_sampling,
-                                        pk->native_colorspace);
-  TORCH_CHECK(why == nullptr, "jpeg_entropy_gpu_parallel: descriptor outside its buffer: ", why ? why : "");
-  auto dev_desc = pk->desc.to(bytes.device());
-  auto dev_sets = pk->sets.to(bytes.device());
-  auto dev_par = pk->par.to(bytes.device());
-  const auto* sp = reinterpret_cast<const JpegHuffSet*>(dev_sets.data_ptr());
-  const auto* dp = reinterpret_cast<const JpegHuffDesc*>(dev_desc.data_ptr());
-  if (pk->n_lane) {
-    jpeg_entropy_launch(bytes.data_ptr<uint8_t>(), sp, dp, coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
-                        (int)pk->n, cur_stream());
-    check_launch("jpeg_entropy");
-  }
-  if (pk->n_par) {
-    jpeg_entropy_par_launch(bytes.data_ptr<uint8_t>(), sp, dp, reinterpret_cast<const JpegParDesc*>(dev_par.data_ptr()),
-                            coefs.data_ptr<int16_t>(), status.data_ptr<int>(),
-                            reinterpret_cast<uint32_t*>(scratch.data_ptr<int>()), (int)pk->n, cur_stream());
-    check_launch("jpeg_entropy_par");
-  }
-  launch_restart("jpeg_entropy_gpu_parallel", pk, bytes, dev_desc, dev_sets, coefs, status);
-  launch_progressive("jpeg_entropy_gpu_parallel", pk, bytes, dev_desc, coefs, status);
+  entropy_launch("jpeg_entropy_gpu_parallel", pk, bytes, coefs, status, &scratch);
 }
 
 // Measurement helper (tools/jpeg_bench.py): the synchronisation rounds the sub-stream kernel needs for
@@ -524,13 +517,9 @@ void jpeg_entropy_gpu_parallel(const std::shared_ptr<JpegHuffPacked>& pk, torch:
 // kernel's sub-stream size and cap.  -1: not an entry that kernel takes; 0: not converged within the cap.
 std::vector<int64_t> jpeg_huff_par_rounds(py::list datas) {
   const int n = (int)datas.size();
-  std::vector<const uint8_t*> ptr(n, nullptr);
-  std::vector<size_t> len(n, 0);
-  for (int i = 0; i < n; ++i) {
-    py::handle o = datas[i];
-    if (!o.is_none()) bytes_span(o, &ptr[i], &len[i]);
-    if (ptr[i] != nullptr && len[i] == 0) ptr[i] = nullptr;
-  }
+  std::vector<const uint8_t*> ptr;
+  std::vector<size_t> len;
+  bytes_list(datas, &ptr, &len);
   std::vector<int64_t> rounds(n, -1);
   py::gil_scoped_release nogil;
   std::vector<JpegHeader> hdr((size_t)n);
@@ -608,20 +597,18 @@ void bind_jpeg(py::module_& m) {
       .def_readonly("n_par", &JpegHuffPacked::n_par)
       .def_readonly("n_lane", &JpegHuffPacked::n_lane)
       .def_readonly("scratch_total", &JpegHuffPacked::scratch_total)
-      .def_readonly("native_progressive", &JpegHuffPacked::native_progressive)
+      .def_property_readonly("native_progressive", [](const JpegHuffPacked& p) { return p.opt.native_progressive; })
       .def_readonly("n_prog", &JpegHuffPacked::n_prog)
       .def_readonly("nscans", &JpegHuffPacked::nscans)
       .def_readonly("ntabs", &JpegHuffPacked::ntabs)
-      .def_readonly("restart_intervals", &JpegHuffPacked::restart_intervals)
+      .def_property_readonly("restart_intervals", [](const JpegHuffPacked& p) { return p.opt.restart_intervals; })
       .def_readonly("rst_items", &JpegHuffPacked::rst_items)
       .def_readonly("n_rst", &JpegHuffPacked::n_rst)
-      .def_readonly("native_sampling", &JpegHuffPacked::native_sampling)
-      .def_readonly("native_colorspace", &JpegHuffPacked::native_colorspace);
+      .def_property_readonly("native_sampling", [](const JpegHuffPacked& p) { return p.opt.native_sampling; })
+      .def_property_readonly("native_colorspace", [](const JpegHuffPacked& p) { return p.opt.native_colorspace; });
   m.def("jpeg_huff_pack", &jpeg_huff_pack,
         "parse a list of bytes / None and pack bytes, Huffman tables and descriptors for the device entropy stage "
-        "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel; restart_intervals: one work item per "
-        "restart interval for the interval kernel; native_sampling: 4:4:0 and 4:1:1 files are accepted; "
-        "native_colorspace: RGB-coded files are classified, 1x1 CMYK / YCCK files are accepted)",
+        "(parallel: the sub-stream layout of jpeg_entropy_gpu_parallel; the other flags: JpegOptions)",
         py::arg("datas"), py::arg("parallel") = false, py::arg("native_progressive") = false,
         py::arg("restart_intervals") = false, py::arg("native_sampling") = false, py::arg("native_colorspace") = false);
   m.attr("JPEG_PROG_MAX_SCANS") = (int64_t)kJpegProgMaxScans;

@@ -306,7 +306,7 @@ void jpeg_entropy_par_launch(const uint8_t* bytes, const JpegHuffSet* sets, cons
                              hipStream_t st);
 // one lane per entry of list[0, nlist), the batch's progressive entries (gpu == 3 in desc[0, n)): every
 // scan of the image with the core of jpeg_huff_prog.h; status[list[j]] is written.  The caller has run
-// jpeg_huff_check(..., allow_prog) and jpeg_huff_prog_check over desc, scans and the table count.
+// jpeg_huff_check (JpegOptions::native_progressive) and jpeg_huff_prog_check over desc, scans and the table count.
 struct JpegHuffTab;
 struct JpegProgScan;
 void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int ntabs, const JpegProgScan* scans,
@@ -315,7 +315,7 @@ void jpeg_entropy_prog_launch(const uint8_t* bytes, const JpegHuffTab* tabs, int
 // one lane per item of items[0, nitems), the restart intervals of the batch's gpu == 4 entries
 // (jpeg_huff_rst.h); a lane whose interval is refused raises status[entry] to JPEG_CORRUPT with an atomic
 // max and a lane that accepts writes nothing, so status must be zero on entry.  The caller has run
-// jpeg_huff_check(..., allow_rst) and jpeg_huff_rst_check over desc and items.
+// jpeg_huff_check (JpegOptions::restart_intervals) and jpeg_huff_rst_check over desc and items.
 struct JpegRstItem;
 void jpeg_entropy_rst_launch(const uint8_t* bytes, const JpegHuffSet* sets, const JpegHuffDesc* desc,
                              const JpegRstItem* items, int nitems, int16_t* coef, int* status, int n,

@@ -5,17 +5,11 @@
 // block that the header-derived layout places inside the output span), so
 // arbitrary bytes give a status, never an out-of-range access.
 //
-// With native_progressive the parser also walks a progressive file's scans up
-// to EOI into a scan script, and jpeg_decode runs the shared scan core of
-// ../jpeg_huff_prog.h over it; baseline files take the same path as without it.
-//
-// With native_sampling the parser also accepts the 4:4:0 (luma 1x2) and 4:1:1
-// (luma 4x1) layouts as modes 3 and 4; the decode loops are the same, they take
-// every h, v in 1..4 from the header.
-//
-// With native_colorspace the marker walk also records JFIF APP0, Adobe APP14 and the
-// component ids, classifies the colour model as libjpeg does (JpegHeader::colorspace) and
-// accepts four components sampled 1x1; the decode loops run over ncomp as before.
+// What JpegOptions admits costs no second path: the parser also walks a progressive file's
+// scans up to EOI into a scan script, which jpeg_decode hands to the shared scan core of
+// ../jpeg_huff_prog.h (baseline files take the same path as without it); the decode loops take
+// every h, v in 1..4 and every ncomp from the header, so modes 3 and 4 and four components run
+// through them unchanged.
 #include "jpeg_entropy.h"
 
 #include <algorithm>
@@ -132,11 +126,10 @@ int script_tab(const RawTabs& raw, int slot, JpegProgScript* script) {
   return (int)script->tabs.size() - 1;
 }
 
-// native: an SOF2 frame is walked to EOI (script, when given, receives its scans)
-// sampling: luma 1x2 and 4x1 over 1x1 chroma are modes 3 and 4, not JPEG_UNSUPPORTED_SAMPLING
-// color: JFIF / Adobe / component ids decide hdr->colorspace, four 1x1 components are taken
-int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, bool native = false,
-          JpegProgScript* script = nullptr, bool sampling = false, bool color = false) {
+// opt: see JpegOptions; script, when given, receives the scans of a progressive file
+int parse(const uint8_t* data, size_t n, JpegHeader* hdr, Tables* tb, Scan* sc, const JpegOptions& opt,
+          JpegProgScript* script = nullptr) {
+  const bool native = opt.native_progressive, sampling = opt.native_sampling, color = opt.native_colorspace;
   if (data == nullptr || n == 0) return JPEG_EMPTY;
   if (n < 2 || data[0] != 0xFF || data[1] != 0xD8) return JPEG_NOT_JPEG;
   std::memset(hdr, 0, sizeof(*hdr));
@@ -484,11 +477,10 @@ const char* jpeg_status_name(int status) {
   return status >= 0 && status < JPEG_STATUS_COUNT ? names[status] : "unknown";
 }
 
-int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive, JpegProgScript* script,
-                      bool native_sampling, bool native_colorspace) {
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, const JpegOptions& opt, JpegProgScript* script) {
   std::vector<Tables> tb(1);                             // ~9 KB: off the stack
   Scan sc;
-  return parse(data, n, hdr, &tb[0], &sc, native_progressive, script, native_sampling, native_colorspace);
+  return parse(data, n, hdr, &tb[0], &sc, opt, script);
 }
 
 void jpeg_prog_frame_desc(const JpegHeader& h, JpegHuffDesc* d) {
@@ -530,14 +522,12 @@ int decode_progressive(const uint8_t* data, size_t n, const JpegHeader& hdr, con
 
 }  // namespace
 
-int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, bool native_progressive,
-                bool native_sampling, bool native_colorspace) {
+int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap, const JpegOptions& opt) {
   std::vector<Tables> tbv(1);
   Tables& tb = tbv[0];
   Scan sc;
   JpegProgScript script;
-  const int st = parse(data, n, hdr, &tb, &sc, native_progressive, native_progressive ? &script : nullptr, native_sampling,
-                       native_colorspace);
+  const int st = parse(data, n, hdr, &tb, &sc, opt, opt.native_progressive ? &script : nullptr);
   if (st != JPEG_OK) return st;
   if (out == nullptr || (size_t)hdr->total_coefs > out_cap) return JPEG_BUFFER_TOO_SMALL;
   std::memset(out, 0, (size_t)hdr->total_coefs * sizeof(int16_t));
@@ -575,16 +565,13 @@ int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, si
 }
 
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
-                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads,
-                       bool native_progressive, bool native_sampling, bool native_colorspace) {
+                       int16_t* const* out, const size_t* out_cap, int* status, int nthreads, const JpegOptions& opt) {
   std::atomic<int> next{0};
   auto work = [&]() {
     for (;;) {
       const int i = next.fetch_add(1);
       if (i >= n) return;
-      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY
-                                     : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], native_progressive, native_sampling,
-                                                   native_colorspace);
+      status[i] = data[i] == nullptr ? (int)JPEG_EMPTY : jpeg_decode(data[i], len[i], &hdr[i], out[i], out_cap[i], opt);
     }
   };
   const int nt = std::max(1, std::min(nthreads, n));

@@ -9,12 +9,8 @@
 // padded block grid (bw x bh = MCU grid x sampling factors); components follow
 // each other at JpegComp::coef_off (in int16 elements).
 //
-// Progressive files (SOF2) are refused unless a caller passes native_progressive;
-// then they decode into the same layout (../jpeg_huff_prog.h).  The 4:4:0 and
-// 4:1:1 chroma layouts are refused unless a caller passes native_sampling.  Without
-// native_colorspace a 3-component file is taken for YCbCr whatever its markers say and a
-// 4-component one is refused; with it the JFIF / Adobe markers and the component ids
-// classify the file as libjpeg does (JpegHeader::colorspace) and 1x1 CMYK / YCCK is decoded.
+// Which files are taken beyond 8-bit baseline 4:4:4 / 4:2:2 / 4:2:0 YCbCr or grey is the caller's
+// choice: JpegOptions below.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -84,29 +80,48 @@ struct JpegProgScript {
   uint32_t first_pos = 0;              // byte offset of the first scan's entropy-coded data in the file
 };
 
-// Parses the markers up to and including SOS.  Fills *hdr on JPEG_OK.
-// native_progressive: an SOF2 frame of a supported layout is not refused with
-// JPEG_UNSUPPORTED_PROGRESSIVE; the walk then goes on over every scan up to EOI
-// (hdr->progressive, hdr->nscans; *script, when given, receives the scan script).
-// It refuses as JPEG_CORRUPT a scan with Ss == 0 and Se != 0, an AC scan of more
-// than one component, Se > 63, Ss > Se, Al > 13, a refinement with Ah != Al + 1,
-// a scan that uses an undefined table and a file without EOI; more than
-// kJpegProgMaxScans scans are JPEG_UNSUPPORTED_MULTISCAN.  A component's
-// quantisation table is the one in its slot at that component's first scan.
-// native_sampling: a 3-component frame whose chroma components are both 1x1 and
-// whose luma is 1x2 or 4x1 is accepted as mode 3 or 4; every other layout beyond
-// modes 0..2 stays JPEG_UNSUPPORTED_SAMPLING.
-// native_colorspace: the colour model is read as libjpeg reads it.  Three components: YCbCr
-// when a JFIF APP0 was seen; else, when an Adobe APP14 was seen (at least 12 bytes, starting
-// with "Adobe"), RGB for its transform byte 0 and YCbCr otherwise; else RGB for the component
-// ids 'R','G','B' and YCbCr for anything else.  Four components, all sampled 1x1 (mode 0; any
-// other sampling is JPEG_UNSUPPORTED_SAMPLING), baseline or progressive: CMYK without an
-// Adobe segment or with transform 0, YCCK with transform 2, JPEG_UNSUPPORTED_COMPONENTS for
-// any other transform.  Without the flag hdr->colorspace is 0 and every 3-component file is
-// decoded as YCbCr downstream, an RGB-coded one included.
-int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool native_progressive = false,
-                      JpegProgScript* script = nullptr, bool native_sampling = false,
-                      bool native_colorspace = false);
+// What a caller takes beyond the default; every member is an opt-in.  One value goes from the
+// Python bindings through the parser, the host decoder, the packer and the descriptor checks, so
+// that all of them agree on which files a batch may hold.
+struct JpegOptions {
+  // An SOF2 frame of a supported layout is not refused with JPEG_UNSUPPORTED_PROGRESSIVE: the
+  // marker walk goes on over every scan up to EOI.  It refuses as JPEG_CORRUPT a scan with
+  // Ss == 0 and Se != 0, an AC scan of more than one component, Se > 63, Ss > Se, Al > 13, a
+  // refinement with Ah != Al + 1, a scan that uses an undefined table and a file without EOI;
+  // more than kJpegProgMaxScans scans are JPEG_UNSUPPORTED_MULTISCAN.  A component's quantisation
+  // table is the one in its slot at that component's first scan.  The host decoder runs the scan
+  // core of ../jpeg_huff_prog.h, the packer gives the file gpu == 3, and the descriptor checks
+  // take gpu == 3 entries (their scans: jpeg_huff_prog_check).
+  bool native_progressive = false;
+  // Packer and descriptor checks only (the parser and the host decoder ignore it): a baseline file
+  // with a restart interval whose RSTn markers the packer finds gets gpu == 4 and one JpegRstItem
+  // per interval, and the checks take gpu == 4 entries (their items: jpeg_huff_rst_check).
+  bool restart_intervals = false;
+  // A 3-component frame whose chroma components are both 1x1 and whose luma is 1x2 (4:4:0) or
+  // 4x1 (4:1:1) is accepted as mode 3 or 4 and laid out like every other file of its kind (gpu 1
+  // to 4); every other layout beyond modes 0..2 stays JPEG_UNSUPPORTED_SAMPLING.  Without it the
+  // descriptor checks refuse an entry with those luma factors, which only a batch planned with
+  // it holds.
+  bool native_sampling = false;
+  // The colour model is read as libjpeg reads it.  Three components: YCbCr when a JFIF APP0 was
+  // seen; else, when an Adobe APP14 was seen (at least 12 bytes, starting with "Adobe"), RGB for
+  // its transform byte 0 and YCbCr otherwise; else RGB for the component ids 'R','G','B' and
+  // YCbCr for anything else.  Four components, all sampled 1x1 (mode 0; any other sampling is
+  // JPEG_UNSUPPORTED_SAMPLING), baseline or progressive: CMYK without an Adobe segment or with
+  // transform 0, YCCK with transform 2, JPEG_UNSUPPORTED_COMPONENTS for any other transform.
+  // Without it hdr->colorspace is 0, every 3-component file is decoded as YCbCr downstream, an
+  // RGB-coded one included, and a 4-component file is refused.  A 4-component file gets gpu == 1,
+  // or gpu == 3 when progressive, whatever par_sub_bits and restart_intervals say (the sub-stream
+  // and interval kernels keep to one and three components); RGB-coded files are laid out like
+  // their YCbCr twins.  Without it the descriptor checks refuse a 4-component entry.
+  bool native_colorspace = false;
+};
+
+// Parses the markers up to and including SOS, taking what opt admits (restart_intervals plays no
+// part here).  Fills *hdr on JPEG_OK.  Of a progressive file the walk goes on over every scan up to
+// EOI (hdr->progressive, hdr->nscans); *script, when given, receives the scan script.
+int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, const JpegOptions& opt = {},
+                      JpegProgScript* script = nullptr);
 
 // The frame layout of *hdr in a JpegHuffDesc (ncomp, MCU grid, per component
 // sampling, padded grid, own grid, coefficient offsets, total_coefs): what
@@ -114,19 +129,17 @@ int jpeg_parse_header(const uint8_t* data, size_t n, JpegHeader* hdr, bool nativ
 void jpeg_prog_frame_desc(const JpegHeader& hdr, JpegHuffDesc* d);
 
 // Parses and decodes one image into out[0, out_cap) (int16 elements).  Never
-// reads outside data[0, n) nor writes outside out[0, out_cap).
-// native_progressive: a progressive file is decoded with the core of
-// jpeg_huff_prog.h on a word-aligned copy of its scans; baseline files are
-// decoded as without it.  native_sampling, native_colorspace: as for jpeg_parse_header.
+// reads outside data[0, n) nor writes outside out[0, out_cap).  opt: as for
+// jpeg_parse_header; a progressive file is decoded with the core of jpeg_huff_prog.h
+// on a word-aligned copy of its scans, baseline files as without the option.
 int jpeg_decode(const uint8_t* data, size_t n, JpegHeader* hdr, int16_t* out, size_t out_cap,
-                bool native_progressive = false, bool native_sampling = false, bool native_colorspace = false);
+                const JpegOptions& opt = {});
 
 // Decodes n images on a pool of `nthreads` std::threads (never derived from
 // the machine's CPU count).  Image i with data[i] == nullptr is skipped with
 // JPEG_EMPTY.  status[i] and hdr[i] are written for every i.
 void jpeg_decode_batch(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr,
                        int16_t* const* out, const size_t* out_cap, int* status, int nthreads = 8,
-                       bool native_progressive = false, bool native_sampling = false,
-                       bool native_colorspace = false);
+                       const JpegOptions& opt = {});
 
 }  // namespace idunno

@@ -141,8 +141,7 @@ size_t destuff(const uint8_t* src, size_t n, uint8_t* dst, size_t cap) {
 }  // namespace
 
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits, bool native_progressive, bool restart_intervals,
-                    bool native_sampling, bool native_colorspace) {
+                    JpegHuffBatch* out, uint32_t par_sub_bits, const JpegOptions& opt) {
   out->desc.assign((size_t)n, JpegHuffDesc{});
   out->sets.clear();
   out->scans.clear();
@@ -163,8 +162,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       status[i] = JPEG_EMPTY;
       continue;
     }
-    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], native_progressive, &script, native_sampling,
-                                  native_colorspace);
+    status[i] = jpeg_parse_header(data[i], len[i], &hdr[i], opt, &script);
     if (status[i] != JPEG_OK) continue;
     const JpegHeader& h = hdr[i];
     if (h.progressive) {
@@ -258,7 +256,7 @@ void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHe
       d.td[c] = rs.td[c];
       d.ta[c] = rs.ta[c];
     }
-    if (restart_intervals && d.gpu == 1 && h.restart_interval > 0 && h.mcux >= 1 && h.mcuy >= 1 && h.ncomp != 4) {
+    if (opt.restart_intervals && d.gpu == 1 && h.restart_interval > 0 && h.mcux >= 1 && h.mcuy >= 1 && h.ncomp != 4) {
       // one item per interval: the byte after each in-sequence RSTn, found by the reader's byte rules
       const int64_t ri = h.restart_interval;
       const int64_t need = ((int64_t)h.mcux * h.mcuy + ri - 1) / ri - 1;
@@ -314,15 +312,15 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 namespace {
 
 const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap, int64_t nsets,
-                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, bool allow_prog, bool allow_rst,
-                      bool allow_sampling, bool allow_colorspace) {
+                      int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits, const JpegOptions& opt) {
   int64_t byte_at = 0, coef_at = 0;       // spans ascend with the entries: none may start before its predecessor ends
   int64_t scratch_at = 0;
   if (par != nullptr && (sub_bits < 32u || sub_bits > kJpegParMaxSubBits || sub_bits % 32u != 0)) return "sub-stream size";
   for (int i = 0; i < n; ++i) {
     const JpegHuffDesc& d = desc[i];
     if (!d.gpu) continue;
-    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr) && !(d.gpu == 3 && allow_prog) && !(d.gpu == 4 && allow_rst))
+    if (d.gpu != 1 && !(d.gpu == 2 && par != nullptr) && !(d.gpu == 3 && opt.native_progressive) &&
+        !(d.gpu == 4 && opt.restart_intervals))
       return "gpu flag";
     if (d.byte_off < byte_at || d.byte_off % kJpegHuffByteAlign != 0 || d.byte_len > d.byte_span ||
         d.byte_span % kJpegHuffBytePad != 0 || d.byte_off + (int64_t)d.byte_span > byte_cap)
@@ -344,11 +342,11 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
       co += (int64_t)d.bw[c] * d.bh[c] * 64;
     }
     if (co != (int64_t)d.total_coefs) return "coefficient count";
-    if (!allow_sampling && d.ncomp == 3 && d.h[1] == 1 && d.v[1] == 1 && d.h[2] == 1 && d.v[2] == 1 &&
+    if (!opt.native_sampling && d.ncomp == 3 && d.h[1] == 1 && d.v[1] == 1 && d.h[2] == 1 && d.v[2] == 1 &&
         ((d.h[0] == 1 && d.v[0] == 2) || (d.h[0] == 4 && d.v[0] == 1)))
       return "sampling layout of a batch planned without native_sampling";
     if (d.ncomp == 4) {
-      if (!allow_colorspace) return "four components in a batch planned without native_colorspace";
+      if (!opt.native_colorspace) return "four components in a batch planned without native_colorspace";
       if (d.gpu == 2 || d.gpu == 4) return "four components outside the one-lane and progressive kernels";
       for (int c = 0; c < 4; ++c)
         if (d.h[c] != 1 || d.v[c] != 1) return "four components not all 1x1";
@@ -372,17 +370,15 @@ const char* check_all(const JpegHuffDesc* desc, const JpegParDesc* par, int n, i
 }  // namespace
 
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog, bool allow_rst, bool allow_sampling, bool allow_colorspace) {
-  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, allow_prog, allow_rst, allow_sampling,
-                   allow_colorspace);
+                            const JpegOptions& opt) {
+  return check_all(desc, nullptr, n, byte_cap, nsets, coef_cap, 0, 0, opt);
 }
 
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog, bool allow_rst, bool allow_sampling, bool allow_colorspace) {
+                                const JpegOptions& opt) {
   if (par == nullptr) return "no sub-stream descriptors";
-  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, allow_prog, allow_rst, allow_sampling,
-                   allow_colorspace);
+  return check_all(desc, par, n, byte_cap, nsets, coef_cap, scratch_cap, sub_bits, opt);
 }
 
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,

@@ -26,10 +26,10 @@ struct JpegHuffBatch {
   // the sub-stream form (jpeg_huff_plan with par_sub_bits != 0), else empty / 0
   std::vector<JpegParDesc> par;     // one per entry, meaningful where desc[i].gpu == 2
   int64_t scratch_total = 0;        // uint32 elements of the batch scratch buffer
-  // progressive files (jpeg_huff_plan with native_progressive), else empty
+  // progressive files (jpeg_huff_plan with opt.native_progressive), else empty
   std::vector<JpegProgScan> scans;  // the scan scripts of the gpu == 3 entries, back to back
   std::vector<JpegHuffTab> tabs;    // the single tables those scans index; identical tables share one entry
-  // restart-interval files (jpeg_huff_plan with restart_intervals), else empty
+  // restart-interval files (jpeg_huff_plan with opt.restart_intervals), else empty
   std::vector<JpegRstItem> rst_items;   // one per interval of the gpu == 4 entries, entry by entry, ascending
 };
 
@@ -41,13 +41,13 @@ struct JpegHuffBatch {
 // restart interval whose scan is shorter than kJpegParMaxBits gets gpu == 2, a byte
 // span sized for its de-stuffed words, a JpegParDesc and a scratch span; every
 // other accepted image keeps gpu == 1 and the stuffed layout of the one-lane kernel.
-// native_progressive: a progressive file of a supported layout is accepted too (else
-// JPEG_UNSUPPORTED_PROGRESSIVE) and gets gpu == 3 in either form: its byte span is
-// the file from the first scan's data to the end in the stuffed layout of gpu == 1,
-// and it names a range of out->scans (jpeg_huff_prog.h), whose tables are entries
-// of out->tabs.
-// restart_intervals: an accepted baseline file with a restart interval is scanned once
-// from scan_pos by the byte rules of jpeg_huff_detail::Bits::fill (FF 00 data, FF FF
+// opt (JpegOptions, jpeg_entropy.h) goes to jpeg_parse_header and decides which of the further
+// layouts the batch may hold:
+// gpu == 3, a progressive file, in either form: its byte span is the file from the first scan's
+// data to the end in the stuffed layout of gpu == 1, and it names a range of out->scans
+// (jpeg_huff_prog.h), whose tables are entries of out->tabs.
+// gpu == 4, with opt.restart_intervals: an accepted baseline file with a restart interval is
+// scanned once from scan_pos by the byte rules of jpeg_huff_detail::Bits::fill (FF 00 data, FF FF
 // fill, any other FF xx a marker) for the byte offset after each in-sequence RSTn, up to
 // the first other marker, an out-of-sequence RSTn or the end.  With at least
 // ceil(mcux * mcuy / ri) - 1 markers (later ones are ignored, as the serial decoder
@@ -56,16 +56,8 @@ struct JpegHuffBatch {
 // restart interval of at least the MCU count needs no marker and is one item.  With
 // fewer markers the serial decoder will refuse the file: it keeps gpu == 1 and the
 // one-lane kernel gives the verdict.  gpu == 2 and gpu == 3 entries are untouched.
-// native_sampling: passed to jpeg_parse_header, so 4:4:0 and 4:1:1 files (modes 3 and 4)
-// are accepted and laid out like every other file of their kind (gpu 1 to 4).
-// native_colorspace: passed to jpeg_parse_header, so hdr[i].colorspace is classified and 1x1
-// four-component files (CMYK, YCCK) are accepted.  A four-component file gets gpu == 1, or
-// gpu == 3 when progressive, in either form and whatever restart_intervals says: the
-// sub-stream and interval kernels keep to one and three components.  RGB-coded
-// three-component files are laid out like their YCbCr twins.
 void jpeg_huff_plan(int n, const uint8_t* const* data, const size_t* len, JpegHeader* hdr, int* status,
-                    JpegHuffBatch* out, uint32_t par_sub_bits = 0, bool native_progressive = false,
-                    bool restart_intervals = false, bool native_sampling = false, bool native_colorspace = false);
+                    JpegHuffBatch* out, uint32_t par_sub_bits = 0, const JpegOptions& opt = {});
 
 // Copies the entropy-coded bytes of every gpu entry to dst[0, byte_total) and
 // zeroes the padding between them.  A gpu == 2 entry gets its de-stuffed words
@@ -77,29 +69,22 @@ void jpeg_huff_copy_bytes(const JpegHuffBatch& b, const uint8_t* const* data, co
 // table sets, coef_cap int16 elements): nullptr when every span lies inside them
 // and the layout inside each span is consistent, else what is wrong.  Run before
 // a launch.
-// allow_prog: gpu == 3 entries are taken (spans and frame; their scans: jpeg_huff_prog_check).
-// allow_rst: gpu == 4 entries are taken (spans, frame, a restart interval; their items: jpeg_huff_rst_check).
-// allow_sampling: a 3-component entry may have luma 1x2 or 4x1 over 1x1 chroma (modes 3 and 4); without it
-// such an entry, which only a batch planned with native_sampling holds, is refused.
-// allow_colorspace: an entry may have four components, all 1x1, with gpu == 1 or 3; without it such an
-// entry, which only a batch planned with native_colorspace holds, is refused.
+// opt: what the batch was planned with; an entry that only another JpegOptions admits is refused.
 const char* jpeg_huff_check(const JpegHuffDesc* desc, int n, int64_t byte_cap, int64_t nsets, int64_t coef_cap,
-                            bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false,
-                            bool allow_colorspace = false);
+                            const JpegOptions& opt = {});
 
 // The same for a batch planned with par_sub_bits: gpu == 1 entries as above, gpu == 2
 // entries also against their JpegParDesc and the scratch buffer (scratch_cap uint32
 // elements, kJpegParStateWords per sub-stream of sub_bits bits).
 const char* jpeg_huff_par_check(const JpegHuffDesc* desc, const JpegParDesc* par, int n, int64_t byte_cap,
                                 int64_t nsets, int64_t coef_cap, int64_t scratch_cap, uint32_t sub_bits,
-                                bool allow_prog = false, bool allow_rst = false, bool allow_sampling = false,
-                                bool allow_colorspace = false);
+                                const JpegOptions& opt = {});
 
 // The gpu == 3 entries against the scan buffer (nscans JpegProgScan) and the table
 // buffer (ntabs JpegHuffTab) the progressive kernel will get: every image's scan
 // range inside the scan buffer, every scan's offset inside the image's byte span,
 // its parameters within what the core accepts, every table index it will use inside
-// the table buffer.  Run next to jpeg_huff_check(..., allow_prog = true) before a launch.
+// the table buffer.  Run next to jpeg_huff_check with opt.native_progressive before a launch.
 const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProgScan* scans, int64_t nscans,
                                  int64_t ntabs);
 
@@ -107,7 +92,7 @@ const char* jpeg_huff_prog_check(const JpegHuffDesc* desc, int n, const JpegProg
 // gpu == 4 entry, byte_begin < byte_len, mcu_first == index * restart_interval <
 // mcux * mcuy; the items of one entry contiguous, ascending and complete (every gpu == 4
 // entry has all ceil(mcux * mcuy / ri) of them, entries ascending); nitems < 2^31.  Run
-// next to jpeg_huff_check(..., allow_rst = true) before a launch.
+// next to jpeg_huff_check with opt.restart_intervals before a launch.
 const char* jpeg_huff_rst_check(const JpegHuffDesc* desc, int n, const JpegRstItem* items, int64_t nitems);
 
 }  // namespace idunno

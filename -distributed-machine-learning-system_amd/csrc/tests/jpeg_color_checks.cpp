@@ -17,7 +17,7 @@
 // jpeg_huff_decode_scan (gpu == 1) or jpeg_prog_decode_image (gpu == 3).  Word span,
 // coefficient span, scans and tables lie in exactly sized heap allocations.  The run must
 // give jpeg_decode's verdict and, where both accept, identical coefficients; the
-// descriptor must pass the checks that run before a launch with allow_colorspace and,
+// descriptor must pass the checks that run before a launch with native_colorspace and,
 // where it has four components, be refused without.
 // It also plans every input in the sub-stream layout, with restart_intervals and with
 // both: a four-component entry must never get gpu == 2 or gpu == 4, and those plans must
@@ -49,12 +49,16 @@ static long g_four = 0, g_four_layouts = 0;     // four-component inputs accepte
     }                                                  \
   } while (0)
 
-static const char* all_checks(const JpegHuffBatch& b, uint32_t S, bool intervals, bool allow_color) {
+// progressive files always, the new samplings never: without and with the colour spaces
+static JpegOptions progressive_only() { JpegOptions o; o.native_progressive = true; return o; }
+static JpegOptions with_colorspace() { JpegOptions o = progressive_only(); o.native_colorspace = true; return o; }
+static const JpegOptions kPlain = progressive_only(), kColor = with_colorspace();
+
+static const char* all_checks(const JpegHuffBatch& b, uint32_t S, const JpegOptions& opt) {
   const int64_t nsets = (int64_t)b.sets.size();
   const char* why = S ? jpeg_huff_par_check(b.desc.data(), b.par.data(), 1, b.byte_total, nsets, b.coef_total,
-                                            b.scratch_total, S, true, intervals, false, allow_color)
-                      : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, true, intervals, false,
-                                        allow_color);
+                                            b.scratch_total, S, opt)
+                      : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, opt);
   if (why == nullptr)
     why = jpeg_huff_prog_check(b.desc.data(), 1, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   if (why == nullptr) why = jpeg_huff_rst_check(b.desc.data(), 1, b.rst_items.data(), (int64_t)b.rst_items.size());
@@ -65,14 +69,15 @@ static const char* all_checks(const JpegHuffBatch& b, uint32_t S, bool intervals
 static void other_layouts(const uint8_t* ptr, size_t n, const char* what, size_t at) {
   for (int f = 1; f < 4; ++f) {
     const uint32_t S = (f & 1) ? kJpegParSubBits : 0u;
-    const bool intervals = (f & 2) != 0;
     JpegHeader hdr;
     int status = -1;
     JpegHuffBatch b;
-    jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, S, true, intervals, false, true);
+    JpegOptions opt = kColor;
+    opt.restart_intervals = (f & 2) != 0;
+    jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, S, opt);
     if (status != JPEG_OK) continue;
     const JpegHuffDesc& d = b.desc[0];
-    const char* why = all_checks(b, S, intervals, true);
+    const char* why = all_checks(b, S, opt);
     CHECK(why == nullptr, "%s@%zu layout %d: descriptor refused: %s\n", what, at, f, why ? why : "");
     if (hdr.ncomp != 4) continue;
     ++g_four_layouts;
@@ -88,19 +93,19 @@ static int run_core(const uint8_t* ptr, size_t n, const char* what, size_t at, s
   JpegHeader hdr;
   int status = -1;
   JpegHuffBatch b;
-  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0u, true, false, false, true);
+  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0u, kColor);
   coefs->clear();
   if (status != JPEG_OK) {
     CHECK(b.desc[0].gpu == 0 && b.rst_items.empty(), "%s@%zu: refused entry marked for the device\n", what, at);
     return status;
   }
   const JpegHuffDesc& d = b.desc[0];
-  const char* why = all_checks(b, 0u, false, true);
+  const char* why = all_checks(b, 0u, kColor);
   CHECK(why == nullptr, "%s@%zu: descriptor refused: %s\n", what, at, why ? why : "");
   if (why != nullptr) return -1;
-  // the same descriptor without allow_colorspace: refused exactly where it has four components
-  const char* plain = all_checks(b, 0u, false, false);
-  CHECK((plain != nullptr) == (d.ncomp == 4), "%s@%zu: check without allow_colorspace: %s\n", what, at,
+  // the same descriptor without native_colorspace: refused exactly where it has four components
+  const char* plain = all_checks(b, 0u, kPlain);
+  CHECK((plain != nullptr) == (d.ncomp == 4), "%s@%zu: check without native_colorspace: %s\n", what, at,
         plain ? plain : "accepted");
   CHECK(d.ncomp == hdr.ncomp, "%s@%zu: %d components in the descriptor, %d in the header\n", what, at, d.ncomp, hdr.ncomp);
   CHECK(d.gpu == (hdr.progressive ? 3 : 1), "%s@%zu: gpu flag %d of a %s file\n", what, at, d.gpu,
@@ -138,9 +143,9 @@ static void compare(const uint8_t* data, size_t n, const char* what, size_t at, 
   const uint8_t* ptr = n ? in.get() : nullptr;
   JpegHeader h;
   std::memset(&h, 0, sizeof(h));
-  const int ps = jpeg_parse_header(ptr, n, &h, true, nullptr, false, true);
+  const int ps = jpeg_parse_header(ptr, n, &h, kColor);
   std::vector<int16_t> want(ps == JPEG_OK ? h.total_coefs : 0, 0);
-  const int hs = jpeg_decode(ptr, n, &h, want.data(), want.size(), true, false, true);
+  const int hs = jpeg_decode(ptr, n, &h, want.data(), want.size(), kColor);
   CHECK(hs != JPEG_OK || (h.ncomp == 4 ? (h.colorspace == 2 || h.colorspace == 3) : h.ncomp == 3 ? h.colorspace <= 1
                                                                                                   : h.colorspace == 0),
         "%s@%zu: colour space %d of %d components\n", what, at, h.colorspace, h.ncomp);
@@ -159,14 +164,14 @@ static void compare(const uint8_t* data, size_t n, const char* what, size_t at, 
             what, c);
     JpegHeader h2;
     std::vector<int16_t> none(want.size(), 0);
-    const int s2 = jpeg_parse_header(ptr, n, &h2, true);
+    const int s2 = jpeg_parse_header(ptr, n, &h2, kPlain);
     if (expect == 1) {
       CHECK(s2 == JPEG_OK && h2.colorspace == 0, "%s: colour space %d without native_colorspace\n", what, h2.colorspace);
-      CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), true) == JPEG_OK && none == want,
+      CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), kPlain) == JPEG_OK && none == want,
             "%s: other coefficients without native_colorspace\n", what);
     } else {
       CHECK(s2 == JPEG_UNSUPPORTED_COMPONENTS, "%s: taken without native_colorspace\n", what);
-      CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), true) == JPEG_UNSUPPORTED_COMPONENTS,
+      CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), kPlain) == JPEG_UNSUPPORTED_COMPONENTS,
             "%s: decoded without native_colorspace\n", what);
     }
   }

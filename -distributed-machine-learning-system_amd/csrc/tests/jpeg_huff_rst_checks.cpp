@@ -46,7 +46,9 @@ static int run_rst(const uint8_t* ptr, size_t n, bool descending, const char* wh
   JpegHeader hdr;
   int status = -1;
   JpegHuffBatch b;
-  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0, false, true);
+  JpegOptions opt;
+  opt.restart_intervals = true;
+  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0, opt);
   coefs->clear();
   *intervals = false;
   if (status != JPEG_OK) {
@@ -54,7 +56,7 @@ static int run_rst(const uint8_t* ptr, size_t n, bool descending, const char* wh
     return status;
   }
   const JpegHuffDesc& d = b.desc[0];
-  const char* why = jpeg_huff_check(b.desc.data(), 1, b.byte_total, (int64_t)b.sets.size(), b.coef_total, false, true);
+  const char* why = jpeg_huff_check(b.desc.data(), 1, b.byte_total, (int64_t)b.sets.size(), b.coef_total, opt);
   CHECK(why == nullptr, "%s@%zu: descriptor refused: %s\n", what, at, why ? why : "");
   if (why != nullptr) return -1;
   why = jpeg_huff_rst_check(b.desc.data(), 1, b.rst_items.data(), (int64_t)b.rst_items.size());

@@ -38,6 +38,9 @@ static long long g_max_trips = 0;
     }                                                  \
   } while (0)
 
+static JpegOptions progressive() { JpegOptions o; o.native_progressive = true; return o; }
+static const JpegOptions kProgressive = progressive();
+
 // packer + core on data[0, n) from its own exactly sized heap copy; returns the verdict
 static int run_packed(const uint8_t* data, size_t n, const char* what, size_t at, std::vector<int16_t>* coefs) {
   std::unique_ptr<uint8_t[]> in(new uint8_t[n ? n : 1]);
@@ -46,7 +49,7 @@ static int run_packed(const uint8_t* data, size_t n, const char* what, size_t at
   JpegHeader hdr;
   int status = -1;
   JpegHuffBatch b;
-  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0, true);
+  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, 0, kProgressive);
   coefs->clear();
   if (status != JPEG_OK) {
     CHECK(b.desc[0].gpu == 0, "%s@%zu: refused entry marked for the device\n", what, at);
@@ -55,7 +58,7 @@ static int run_packed(const uint8_t* data, size_t n, const char* what, size_t at
   const JpegHuffDesc& d = b.desc[0];
   CHECK(d.gpu == 3 && hdr.progressive == 1, "%s@%zu: accepted entry is not a progressive one\n", what, at);
   if (d.gpu != 3) return -1;
-  const char* why = jpeg_huff_check(b.desc.data(), 1, b.byte_total, (int64_t)b.sets.size(), b.coef_total, true);
+  const char* why = jpeg_huff_check(b.desc.data(), 1, b.byte_total, (int64_t)b.sets.size(), b.coef_total, kProgressive);
   if (why == nullptr)
     why = jpeg_huff_prog_check(b.desc.data(), 1, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   CHECK(why == nullptr, "%s@%zu: descriptor refused: %s\n", what, at, why ? why : "");
@@ -89,9 +92,9 @@ static void compare(const uint8_t* data, size_t n, const char* what, size_t at, 
   const int st = run_packed(data, n, what, at, &got);
   JpegHeader h;
   std::memset(&h, 0, sizeof(h));
-  const int ps = jpeg_parse_header(n ? data : nullptr, n, &h, true);
+  const int ps = jpeg_parse_header(n ? data : nullptr, n, &h, kProgressive);
   std::vector<int16_t> host(ps == JPEG_OK ? h.total_coefs : 0, 0);
-  const int hs = jpeg_decode(n ? data : nullptr, n, &h, host.data(), host.size(), true);
+  const int hs = jpeg_decode(n ? data : nullptr, n, &h, host.data(), host.size(), kProgressive);
   CHECK(st == hs, "%s@%zu: packed path %d, host path %d\n", what, at, st, hs);
   if (want != nullptr) {
     CHECK(hs == JPEG_OK && st == JPEG_OK, "%s: status %d / %d, expected ok\n", what, hs, st);

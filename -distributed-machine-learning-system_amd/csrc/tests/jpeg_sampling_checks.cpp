@@ -26,7 +26,7 @@
 // jpeg_huff_decode_scan.  Word span, coefficient span, state span, scans and tables lie
 // in exactly sized heap allocations.  Every run must give jpeg_decode's verdict and,
 // where both accept, identical coefficients; every descriptor must pass the checks that
-// run before a launch with allow_sampling and, where its layout is a new one, be refused
+// run before a launch with native_sampling and, where its layout is a new one, be refused
 // without.
 // Build + run: tests/test_jpeg_sampling_checks.py.  Exit status = number of failures.
 #include <cstdio>
@@ -99,6 +99,11 @@ static int run_substreams(const JpegHuffBatch& b, const uint32_t* span, const Jp
   return verdict;
 }
 
+// progressive files always, the colour spaces never: without and with the new samplings
+static JpegOptions progressive_only() { JpegOptions o; o.native_progressive = true; return o; }
+static JpegOptions with_sampling() { JpegOptions o = progressive_only(); o.native_sampling = true; return o; }
+static const JpegOptions kPlain = progressive_only(), kSampling = with_sampling();
+
 // packer + the form's core(s) on data[0, n); returns the verdict (the parse's when it refuses)
 static int run_form(const uint8_t* ptr, size_t n, Form form, const char* what, size_t at, std::vector<int16_t>* coefs) {
   JpegHeader hdr;
@@ -106,7 +111,9 @@ static int run_form(const uint8_t* ptr, size_t n, Form form, const char* what, s
   JpegHuffBatch b;
   const uint32_t S = form == kParSmall ? 32u : (form == kParKernel ? kJpegParSubBits : 0u);
   const bool intervals = form == kIntervals;
-  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, S, true, intervals, true);
+  JpegOptions opt = kSampling, plain_opt = kPlain;
+  opt.restart_intervals = plain_opt.restart_intervals = intervals;
+  jpeg_huff_plan(1, &ptr, &n, &hdr, &status, &b, S, opt);
   coefs->clear();
   if (status != JPEG_OK) {
     CHECK(b.desc[0].gpu == 0 && b.rst_items.empty(), "%s@%zu %s: refused entry marked for the device\n", what, at,
@@ -116,18 +123,18 @@ static int run_form(const uint8_t* ptr, size_t n, Form form, const char* what, s
   const JpegHuffDesc& d = b.desc[0];
   const int64_t nsets = (int64_t)b.sets.size();
   const char* why = S ? jpeg_huff_par_check(b.desc.data(), b.par.data(), 1, b.byte_total, nsets, b.coef_total,
-                                            b.scratch_total, S, true, intervals, true)
-                      : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, true, intervals, true);
+                                            b.scratch_total, S, opt)
+                      : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, opt);
   if (why == nullptr)
     why = jpeg_huff_prog_check(b.desc.data(), 1, b.scans.data(), (int64_t)b.scans.size(), (int64_t)b.tabs.size());
   if (why == nullptr) why = jpeg_huff_rst_check(b.desc.data(), 1, b.rst_items.data(), (int64_t)b.rst_items.size());
   CHECK(why == nullptr, "%s@%zu %s: descriptor refused: %s\n", what, at, kFormName[form], why ? why : "");
   if (why != nullptr) return -1;
-  // the same descriptor without allow_sampling: refused exactly where the layout is one of the new two
+  // the same descriptor without native_sampling: refused exactly where the layout is one of the new two
   const char* plain = S ? jpeg_huff_par_check(b.desc.data(), b.par.data(), 1, b.byte_total, nsets, b.coef_total,
-                                              b.scratch_total, S, true, intervals)
-                        : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, true, intervals);
-  CHECK((plain != nullptr) == new_layout(d), "%s@%zu %s: check without allow_sampling: %s\n", what, at, kFormName[form],
+                                              b.scratch_total, S, plain_opt)
+                        : jpeg_huff_check(b.desc.data(), 1, b.byte_total, nsets, b.coef_total, plain_opt);
+  CHECK((plain != nullptr) == new_layout(d), "%s@%zu %s: check without native_sampling: %s\n", what, at, kFormName[form],
         plain ? plain : "accepted");
   const bool flag_ok = d.gpu == 1 || d.gpu == 3 || (d.gpu == 2 && S) || (d.gpu == 4 && intervals);
   CHECK(flag_ok, "%s@%zu %s: gpu flag %d\n", what, at, kFormName[form], d.gpu);
@@ -179,9 +186,9 @@ static void compare(const uint8_t* data, size_t n, const char* what, size_t at, 
   const uint8_t* ptr = n ? in.get() : nullptr;
   JpegHeader h;
   std::memset(&h, 0, sizeof(h));
-  const int ps = jpeg_parse_header(ptr, n, &h, true, nullptr, true);
+  const int ps = jpeg_parse_header(ptr, n, &h, kSampling);
   std::vector<int16_t> want(ps == JPEG_OK ? h.total_coefs : 0, 0);
-  const int hs = jpeg_decode(ptr, n, &h, want.data(), want.size(), true, true);
+  const int hs = jpeg_decode(ptr, n, &h, want.data(), want.size(), kSampling);
   for (int f = 0; f < 4; ++f) {
     std::vector<int16_t> got;
     const int st = run_form(ptr, n, (Form)f, what, at, &got);
@@ -199,9 +206,9 @@ static void compare(const uint8_t* data, size_t n, const char* what, size_t at, 
     CHECK((h.mode == 3 && h.comp[0].h == 1 && h.comp[0].v == 2) || (h.mode == 4 && h.comp[0].h == 4 && h.comp[0].v == 1),
           "%s: mode %d with luma %dx%d\n", what, h.mode, h.comp[0].h, h.comp[0].v);
     JpegHeader h2;
-    CHECK(jpeg_parse_header(ptr, n, &h2, true) == JPEG_UNSUPPORTED_SAMPLING, "%s: taken without native_sampling\n", what);
+    CHECK(jpeg_parse_header(ptr, n, &h2, kPlain) == JPEG_UNSUPPORTED_SAMPLING, "%s: taken without native_sampling\n", what);
     std::vector<int16_t> none(want.size(), 0);
-    CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), true) == JPEG_UNSUPPORTED_SAMPLING,
+    CHECK(jpeg_decode(ptr, n, &h2, none.data(), none.size(), kPlain) == JPEG_UNSUPPORTED_SAMPLING,
           "%s: decoded without native_sampling\n", what);
   }
   if (hs == JPEG_OK) ++g_both_ok;

@@ -353,23 +353,21 @@ def synth_images(seed: int, start: int, n: int, device, hw: int = 224):
 
 # ---- JPEG decode (runtime/jpeg.py drives these) ---------------------------------------
 
-def jpeg_parse(data: bytes, native_progressive: bool = False, native_sampling: bool = False):
+# The ``native_progressive`` / ``restart_intervals`` / ``native_sampling`` / ``native_colorspace``
+# flags below are the members of ``JpegOptions`` (csrc/runtime/jpeg_entropy.h), where each is
+# documented; all default to ``False``.
+
+def jpeg_parse(data: bytes, native_progressive: bool = False, native_sampling: bool = False,
+               native_colorspace: bool = False):
     """Markers of a JPEG up to SOS: (status, reason, header dict or None);
-    status 0 = a baseline file the native decoder takes.  With
-    ``native_progressive`` a progressive file is walked up to EOI and taken too;
-    with ``native_sampling`` a 4:4:0 or 4:1:1 frame is taken as ``mode`` 3 or 4.
-    The header's ``colorspace`` is 0 here: every three-component file counts as
-    YCbCr, an RGB-coded one included (``jpeg_parse_colorspace`` reads it)."""
-    return load().jpeg_parse(data, bool(native_progressive), bool(native_sampling))
-
-
-def jpeg_parse_colorspace(data: bytes, native_progressive: bool = False, native_sampling: bool = False,
-                          native_colorspace: bool = True):
-    """``jpeg_parse`` with the extension's fourth argument (``jpeg_parse`` itself keeps
-    its three parameters, which tests/test_jpeg_sampling_cpu.py pins): with
-    ``native_colorspace`` the header's ``colorspace`` says what the JFIF /
-    Adobe markers and the component ids make of the samples (0 YCbCr or grey,
-    1 RGB, 2 CMYK, 3 YCCK) and a four-component frame sampled 1x1 is taken."""
+    status 0 = a file the native decoder takes: baseline 4:4:4 / 4:2:2 / 4:2:0,
+    with ``native_progressive`` a progressive file (walked up to EOI), with
+    ``native_sampling`` a 4:4:0 or 4:1:1 frame (``mode`` 3 or 4), with
+    ``native_colorspace`` a four-component frame sampled 1x1.  The header's
+    ``colorspace`` (0 YCbCr or grey, 1 RGB, 2 CMYK, 3 YCCK) is read from the
+    JFIF / Adobe markers and the component ids only with ``native_colorspace``;
+    else it is 0 and every three-component file counts as YCbCr, an RGB-coded
+    one included."""
     return load().jpeg_parse(data, bool(native_progressive), bool(native_sampling), bool(native_colorspace))
 
 
@@ -377,8 +375,8 @@ def jpeg_entropy_batch(datas, threads: int = 8, native_progressive: bool = False
                        native_colorspace: bool = False):
     """Huffman-decode a list of ``bytes | None`` on ``threads`` native threads
     (GIL released): (status per entry, headers, int16 coefficients on the
-    host, first coefficient of each entry or -1).  ``native_colorspace``: as
-    for ``jpeg_parse``; 1x1 CMYK / YCCK files are decoded too."""
+    host, first coefficient of each entry or -1).  The flags: as for
+    ``jpeg_parse``; what it takes is decoded too."""
     return load().jpeg_entropy_batch(datas, int(threads), bool(native_progressive), bool(native_sampling),
                                      bool(native_colorspace))
 
@@ -411,12 +409,11 @@ def jpeg_huff_pack(datas, parallel: bool = False, native_progressive: bool = Fal
     interval in ``rst_items`` (int32 ``[items, 4]``: entry, first byte, first
     MCU, interval index) for the interval kernel, which the same two calls
     launch; ``n_lane`` keeps counting the entries of the one-lane kernel.
-    ``native_sampling``: 4:4:0 and 4:1:1 files are accepted (modes 3 and 4 in
-    their header rows) and packed like every other file of their kind.
-    ``native_colorspace``: the header rows' ``colorspace`` is classified and
-    1x1 CMYK / YCCK files are accepted, always for the one-lane kernel or, when
-    progressive, the progressive one; RGB-coded files are packed like their
-    YCbCr twins.  The batch remembers the flag in ``native_colorspace``."""
+    ``native_sampling`` and ``native_colorspace``: as for ``jpeg_parse``; 4:4:0
+    and 4:1:1 files are packed like every other file of their kind, RGB-coded
+    files like their YCbCr twins, and 1x1 CMYK / YCCK files always for the
+    one-lane kernel or, when progressive, the progressive one.  The batch
+    remembers the four flags in attributes of the same names."""
     return load().jpeg_huff_pack(datas, bool(parallel), bool(native_progressive), bool(restart_intervals),
                                  bool(native_sampling), bool(native_colorspace))
 

@@ -672,11 +672,9 @@ class GpuJpegSource:
 
         from . import jpeg
 
-        self.entropy_on = jpeg._check_entropy_on(entropy_on)
-        self.progressive = jpeg._check_progressive(progressive)
-        self.restart = jpeg._check_restart(restart)
-        self.sampling = jpeg._check_sampling(sampling)
-        self.colorspace = jpeg._check_colorspace(colorspace)
+        self.entropy_on = jpeg._check("entropy_on", entropy_on)
+        jpeg.Options(progressive, restart, sampling, colorspace)      # validates
+        self.progressive, self.restart, self.sampling, self.colorspace = progressive, restart, sampling, colorspace
         self.device = torch.device(device)
         self.root, self.sdfs, self.prefix = root, sdfs, prefix
         self.cache_bytes = int(cache_bytes)

@@ -53,8 +53,9 @@ whose components are all sampled 1x1 is CMYK (no Adobe segment, or transform
 0) or YCCK (transform 2).  RGB-coded files are decoded wherever their YCbCr
 twins are; four-component files take the one-lane kernel (the progressive
 kernel when progressive) in both device forms.  The colour stage of the
-resize kernel hands RGB planes on as they are and converts CMYK / YCCK with
-Pillow's integer formula, on planes the fp64 IDCT pass has rewritten.  Under
+resize kernel hands RGB planes on as they are (planes 1 and 2 upsampled like
+chroma) and converts CMYK / YCCK with the integer formula of Pillow's
+``convert("RGB")``, on planes the fp64 IDCT pass has rewritten.  Under
 the default ``"ycbcr"`` nothing of this is read: a four-component file is a
 ``"components"`` fallback, and an RGB-coded three-component file is decoded
 as YCbCr, which gives wrong colours without a fallback being reported.
@@ -73,6 +74,7 @@ path.  ``reference_backend`` is the float64 numpy model of the GPU chain.
 from __future__ import annotations
 
 import time
+from dataclasses import dataclass, replace
 
 import numpy as np
 import torch
@@ -90,41 +92,48 @@ def _C():
 
 
 PROGRESSIVE = ("fallback", "native")
-
-
-def _check_progressive(progressive: str) -> str:
-    if progressive not in PROGRESSIVE:
-        raise ValueError(f"progressive must be one of {PROGRESSIVE}, not {progressive!r}")
-    return progressive
-
-
 RESTART = ("lane", "intervals")
-
-
-def _check_restart(restart: str) -> str:
-    if restart not in RESTART:
-        raise ValueError(f"restart must be one of {RESTART}, not {restart!r}")
-    return restart
-
-
 SAMPLING = ("fallback", "native")
-
-
-def _check_sampling(sampling: str) -> str:
-    if sampling not in SAMPLING:
-        raise ValueError(f"sampling must be one of {SAMPLING}, not {sampling!r}")
-    return sampling
-
-
 COLORSPACE = ("ycbcr", "auto")
+ENTROPY_ON = ("host", "gpu", "gpu_parallel")
 # header["colorspace"]: what the samples of a file are
 CS_YCBCR, CS_RGB, CS_CMYK, CS_YCCK = 0, 1, 2, 3
 
+_ALLOWED = {"entropy_on": ENTROPY_ON, "progressive": PROGRESSIVE, "restart": RESTART, "sampling": SAMPLING,
+            "colorspace": COLORSPACE}
 
-def _check_colorspace(colorspace: str) -> str:
-    if colorspace not in COLORSPACE:
-        raise ValueError(f"colorspace must be one of {COLORSPACE}, not {colorspace!r}")
-    return colorspace
+
+def _check(name: str, value: str) -> str:
+    if value not in _ALLOWED[name]:
+        raise ValueError(f"{name} must be one of {_ALLOWED[name]}, not {value!r}")
+    return value
+
+
+@dataclass(frozen=True)
+class Options:
+    """What the decoder takes beyond the default (the module docstring says what
+    each value means), validated on construction.  The ``native_*`` /
+    ``restart_intervals`` properties are the booleans of the same names that
+    ``ops.jpeg_parse``, ``ops.jpeg_entropy_batch`` and ``ops.jpeg_huff_pack`` take."""
+    progressive: str = "fallback"
+    restart: str = "lane"
+    sampling: str = "fallback"
+    colorspace: str = "ycbcr"
+
+    def __post_init__(self):
+        for name in ("progressive", "restart", "sampling", "colorspace"):
+            _check(name, getattr(self, name))
+
+    native_progressive = property(lambda self: self.progressive == "native")
+    restart_intervals = property(lambda self: self.restart == "intervals")
+    native_sampling = property(lambda self: self.sampling == "native")
+    native_colorspace = property(lambda self: self.colorspace == "auto")
+
+    @property
+    def parse_flags(self) -> dict:
+        """The keyword arguments of ``ops.jpeg_parse`` / ``ops.jpeg_entropy_batch`` (``restart`` plays no part there)."""
+        return {"native_progressive": self.native_progressive, "native_sampling": self.native_sampling,
+                "native_colorspace": self.native_colorspace}
 
 
 def parse(data: bytes, progressive: str = "fallback", sampling: str = "fallback", colorspace: str = "ycbcr"):
@@ -137,24 +146,19 @@ def parse(data: bytes, progressive: str = "fallback", sampling: str = "fallback"
     (RGB), 2 (CMYK) or 3 (YCCK) and a four-component file sampled 1x1 is taken;
     with the default ``"ycbcr"`` it is always 0, a four-component file is
     ``"components"`` and an RGB-coded file is decoded as YCbCr."""
-    native = _check_progressive(progressive) == "native"
-    samp = _check_sampling(sampling) == "native"
-    color = _check_colorspace(colorspace) == "auto"
-    st, reason, hdr = _C().jpeg_parse_colorspace(bytes(data), native, samp, color)
+    opts = Options(progressive=progressive, sampling=sampling, colorspace=colorspace)
+    st, reason, hdr = _C().jpeg_parse(bytes(data), **opts.parse_flags)
     return hdr if st == 0 else reason
 
 
 def entropy_decode(data: bytes, progressive: str = "fallback", sampling: str = "fallback", colorspace: str = "ycbcr"):
     """(header, int16 coefficients) of one image by the native host decoder, or
     the reason (str) it was refused.  ``colorspace``: as for ``parse``."""
-    native = _check_progressive(progressive) == "native"
-    samp = _check_sampling(sampling) == "native"
-    color = _check_colorspace(colorspace) == "auto"
+    opts = Options(progressive=progressive, sampling=sampling, colorspace=colorspace)
     data = bytes(data)
-    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, native, samp, color)
+    status, _, coefs, offs = _C().jpeg_entropy_batch([data], 1, **opts.parse_flags)
     if status[0] != 0:
-        st, reason, _ = _C().jpeg_parse_colorspace(data, native, samp, color)
-        return reason if st != 0 else "corrupt"
+        return _refusal(_C(), data, status[0], opts)
     return parse(data, progressive, sampling, colorspace), coefs.numpy()
 
 
@@ -319,24 +323,38 @@ def _stager(device: torch.device) -> HbmStager:
     return st
 
 
-ENTROPY_ON = ("host", "gpu", "gpu_parallel")
 _DEVICE_FORMS = ("gpu", "gpu_parallel")
 _UNSYNCED = 100           # kJpegHuffUnsynced: the sub-stream kernel's rounds hit their cap (device-only status)
 
 
-def _refusal(C, data: bytes, status: int, native: bool = False, samp: bool = False, color: bool = False) -> str:
-    """Why an entry is a fallback: the parse's reason (in the progressive, sampling and colorspace
-    modes the batch was decoded in), else what the entropy stage said."""
-    st, reason, _ = C.jpeg_parse_colorspace(data, native, samp, color)
+def _refusal(C, data: bytes, status: int, opts: Options) -> str:
+    """Why an entry is a fallback: the parse's reason (under the options the batch
+    was decoded with), else what the entropy stage said."""
+    st, reason, _ = C.jpeg_parse(data, **opts.parse_flags)
     if st != 0:
         return reason
     return "unsynced" if status == _UNSYNCED else "corrupt"
 
 
-def _check_entropy_on(entropy_on: str) -> str:
-    if entropy_on not in ENTROPY_ON:
-        raise ValueError(f"entropy_on must be one of {ENTROPY_ON}, not {entropy_on!r}")
-    return entropy_on
+def _header_column(hdr, byte_offset: int) -> np.ndarray:
+    """One int field of every row of ``hdr`` (uint8 [n, sizeof(JpegHeader)]) by its
+    byte offset in the struct (``W`` 0, ``H`` 4, ``ops.JPEG_HEADER_*_OFFSET``)."""
+    return hdr.numpy().view(np.int32)[:, byte_offset // 4]
+
+
+@dataclass(frozen=True)
+class Entropy:
+    """What ``entropy_batch`` prepared and ``decode_batch(..., entropy=)`` takes."""
+    form: str                 # the ``entropy_on`` it was prepared in
+    datas: list               # the entries as ``bytes | None``
+    options: Options          # what it was prepared with (the host form does nothing with ``restart``)
+    status: list              # per entry: the host decoder's verdict; in the device forms the parse's
+    hdr: torch.Tensor         # uint8 [n, sizeof(JpegHeader)]
+    offs: list                # first coefficient of each entry whose header parsed, else -1
+    coef_elems: int           # int16 elements of the batch's coefficients
+    coefs: torch.Tensor | None    # host form: the coefficients (CPU)
+    packed: object | None         # device forms: the ``JpegHuffPacked`` of ``ops.jpeg_huff_pack``
+    seconds: float            # wall seconds of the decode (host form) or of parse + pack
 
 
 def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive: str = "fallback",
@@ -352,20 +370,20 @@ def entropy_batch(datas, threads: int = 8, entropy_on: str = "host", progressive
     form is unchanged by it); ``sampling="native"`` takes 4:4:0 and 4:1:1 files
     in every form; ``colorspace="auto"`` classifies RGB-coded files and takes
     1x1 CMYK / YCCK files in every form (under the default every
-    three-component file counts as YCbCr, an RGB-coded one included).  Returns what ``decode_batch(..., entropy=)`` takes; the
-    result remembers the options."""
-    _check_entropy_on(entropy_on)
-    native = _check_progressive(progressive) == "native"
-    intervals = _check_restart(restart) == "intervals"
-    samp = _check_sampling(sampling) == "native"
-    color = _check_colorspace(colorspace) == "auto"
+    three-component file counts as YCbCr, an RGB-coded one included).  Returns
+    an ``Entropy``, which remembers the form and the options."""
+    _check("entropy_on", entropy_on)
+    opts = Options(progressive, restart, sampling, colorspace)
     datas = [None if d is None else bytes(d) for d in datas]
     t0 = time.perf_counter()
     if entropy_on in _DEVICE_FORMS:
-        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp, color)
-        return entropy_on, datas, packed, time.perf_counter() - t0
-    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), native, samp, color)
-    return datas, status, hdr, coefs, offs, time.perf_counter() - t0, progressive, sampling, colorspace
+        packed = _C().jpeg_huff_pack(datas, entropy_on == "gpu_parallel", opts.native_progressive,
+                                     opts.restart_intervals, opts.native_sampling, opts.native_colorspace)
+        return Entropy(entropy_on, datas, opts, list(packed.status), packed.hdr, list(packed.offs),
+                       int(packed.coef_total), None, packed, time.perf_counter() - t0)
+    status, hdr, coefs, offs = _C().jpeg_entropy_batch(datas, int(threads), **opts.parse_flags)
+    return Entropy("host", datas, opts, list(status), hdr, list(offs), coefs.numel(), coefs, None,
+                   time.perf_counter() - t0)
 
 
 def _entropy_on_device(C, packed, device, cur, stager: HbmStager, info: dict):
@@ -405,40 +423,30 @@ def entropy_coefs(datas, device="cpu", entropy_on: str = "host", threads: int = 
     status per entry (0: decoded), the first coefficient of each entry whose
     header parsed in ``coefs`` (-1: none) and the batch's int16 coefficients as a CPU tensor,
     from the host decoder or, with ``entropy_on="gpu"`` / ``"gpu_parallel"`` on a
-    GPU ``device``, from the entropy kernels.  ``progressive="native"``:
-    progressive files are decoded too, in every form.  ``restart="intervals"``:
-    the device forms decode restart-interval files one interval per lane.
-    ``sampling="native"``: 4:4:0 and 4:1:1 files are decoded too, in every form.
-    ``colorspace="auto"``: 1x1 CMYK / YCCK files are decoded too, in every form
-    (on the one-lane or the progressive kernel in the device forms)."""
-    _check_entropy_on(entropy_on)
-    native = _check_progressive(progressive) == "native"
-    intervals = _check_restart(restart) == "intervals"
-    samp = _check_sampling(sampling) == "native"
-    color = _check_colorspace(colorspace) == "auto"
-    C = _C()
-    datas = [None if d is None else bytes(d) for d in datas]
-    if entropy_on == "host":
-        status, _, coefs, offs = C.jpeg_entropy_batch(datas, int(threads), native, samp, color)
-        return list(status), list(offs), coefs
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    packed = C.jpeg_huff_pack(datas, entropy_on == "gpu_parallel", native, intervals, samp, color)
-    status = list(packed.status)
-    coefs = torch.zeros(packed.coef_total, dtype=torch.int16)
-    if packed.n_gpu:
+    GPU ``device``, from the entropy kernels.  The four options: as for
+    ``entropy_batch``."""
+    _check("entropy_on", entropy_on)
+    Options(progressive, restart, sampling, colorspace)
+    if entropy_on in _DEVICE_FORMS:
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"entropy_on={entropy_on!r} needs a GPU device")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+    ent = entropy_batch(datas, threads, entropy_on, progressive, restart, sampling, colorspace)
+    if ent.packed is None:
+        return ent.status, ent.offs, ent.coefs
+    status, coefs = ent.status, torch.zeros(ent.coef_elems, dtype=torch.int16)
+    if ent.packed.n_gpu:
         with torch.cuda.device(device):
             cur = torch.cuda.current_stream(device)
-            dev_coefs, dev_status, _ = _entropy_on_device(C, packed, device, cur, _stager(device), {})
+            dev_coefs, dev_status, _ = _entropy_on_device(_C(), ent.packed, device, cur, _stager(device), {})
             cur.synchronize()
             coefs = dev_coefs.cpu()
             for i, st in enumerate(dev_status.cpu().tolist()):
                 if status[i] == 0:
                     status[i] = int(st)
-    return status, list(packed.offs), coefs
+    return status, ent.offs, coefs
 
 
 def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224, threads: int = 8,
@@ -471,101 +479,73 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     whose sub-streams did not synchronise within the kernel's round cap is an
     ``"unsynced"`` fallback.
 
+    ``progressive``, ``restart``, ``sampling`` and ``colorspace``: the module
+    docstring says what each value takes and which kernel decodes it.  When
+    ``entropy`` was prepared, the form and the options it was prepared with
+    decide, not the arguments here, and ``info["entropy_on"]``,
+    ``info["progressive"]``, ``info["restart"]``, ``info["sampling"]`` and
+    ``info["colorspace"]`` name what is in effect; only ``info["restart"]`` of
+    an ``entropy`` prepared in the host form is the one asked for here (the
+    host form does nothing with it).  On a CPU device nothing native runs.
+
     ``progressive="native"`` (default ``"fallback"``: a progressive file goes
     to ``load_image_u8`` with the reason ``"progressive"``) decodes progressive
     files of a supported layout (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 /
     4:2:0, Huffman, at most ``JPEG_PROG_MAX_SCANS`` scans) natively in every
-    ``entropy_on`` form: on the host threads with the scan core of
-    csrc/jpeg_huff_prog.h, on the device with jpeg_entropy_prog_kernel, one
-    lane per image in both device forms (no sub-stream form for progressive
-    scans).  They hold the coefficients of their baseline twins, so the IDCT
-    and resize kernels see no difference.  A progressive file the decoder or
-    kernel refuses is then a ``"corrupt"`` fallback, one with more scans a
-    ``"multiscan"`` one.  ``info["progressive"]`` names the mode in effect
-    (when ``entropy`` was prepared, the one it was prepared in; on a CPU device
-    the one asked for, and nothing native runs), ``info["progressive_images"]``
-    counts the progressive files decoded natively.  Non-interleaved baseline
-    files (``"multiscan"``), arithmetic coding, 12-bit samples and CMYK remain
+    ``entropy_on`` form.  They hold the coefficients of their baseline twins,
+    so the IDCT and resize kernels see no difference.  A progressive file the
+    decoder or kernel refuses is then a ``"corrupt"`` fallback, one with more
+    scans a ``"multiscan"`` one.  ``info["progressive_images"]`` counts the
+    progressive files decoded natively.  Non-interleaved baseline files
+    (``"multiscan"``), arithmetic coding, 12-bit samples and CMYK remain
     fallbacks.
 
     ``restart="intervals"`` (default ``"lane"``: a baseline file with a restart
     interval is walked by one lane of the one-lane kernel in both device forms)
-    decodes such a file one restart interval per lane
-    (jpeg_entropy_rst_kernel, csrc/jpeg_huff_rst.h) in ``"gpu"`` and
+    decodes such a file one restart interval per lane in ``"gpu"`` and
     ``"gpu_parallel"``; the packer finds the ``RSTn`` markers, and a file that
     lacks one stays with the one-lane kernel, which refuses it.  An image one of
     whose intervals is refused is a ``"corrupt"`` fallback like any other.
     Progressive files with restart markers stay on the progressive kernel.
-    ``info["restart"]`` names the mode in effect (when ``entropy`` was prepared
-    in a device form, the one it was prepared in; on a CPU device and in the
-    host form the one asked for, and nothing changes there),
     ``info["restart_images"]`` counts the images the interval kernel decoded
     and did not flag.
 
     ``sampling="native"`` (default ``"fallback"``: a 4:4:0 or 4:1:1 file goes
-    to ``load_image_u8`` with the reason ``"sampling"``) decodes 3-component
-    files whose chroma components are 1x1 and whose luma is 1x2 (4:4:0, header
-    ``mode`` 3) or 4x1 (4:1:1, ``mode`` 4) natively in every ``entropy_on``
-    form, baseline, restart-interval and progressive alike: the entropy cores
-    take the factors from the header, the resize kernel upsamples mode 3 with
-    libjpeg's vertical triangle filter and mode 4 by replication.  Every other
-    layout stays a ``"sampling"`` fallback.  ``info["sampling"]`` names the
-    mode in effect (when ``entropy`` was prepared, the one it was prepared in;
-    on a CPU device the one asked for, and nothing native runs),
-    ``info["sampling_images"]`` counts the mode-3 and mode-4 images decoded
-    natively and not flagged.
+    to ``load_image_u8`` with the reason ``"sampling"``) decodes those two
+    layouts (header ``mode`` 3 and 4) natively in every ``entropy_on`` form,
+    baseline, restart-interval and progressive alike.  Every other layout
+    stays a ``"sampling"`` fallback.  ``info["sampling_images"]`` counts the
+    mode-3 and mode-4 images decoded natively and not flagged.
 
-    ``colorspace="auto"`` (default ``"ycbcr"``) reads each file's colour model
-    as libjpeg does.  Three components: YCbCr when the file has a JFIF APP0;
-    else RGB for an Adobe APP14 with transform 0 and YCbCr for any other
-    transform; else RGB for the component ids ``R``, ``G``, ``B`` and YCbCr
-    otherwise.  Four components, all sampled 1x1, baseline or (with
-    ``progressive="native"``) progressive, with or without restart markers:
-    CMYK without an Adobe segment or with transform 0, YCCK with transform 2;
-    any other transform stays a ``"components"`` fallback and any other
-    four-component sampling is a ``"sampling"`` one.  RGB-coded files go
-    through whichever entropy kernel their YCbCr twins take; four-component
-    files take the one-lane kernel (or the progressive one) under ``"gpu"``,
-    ``"gpu_parallel"`` and ``restart="intervals"`` alike.  The resize kernel
-    hands RGB planes on as they are (planes 1 and 2 upsampled like chroma) and
-    converts CMYK / YCCK as Pillow's ``convert("RGB")`` does, in integers.
-    Under the default ``"ycbcr"`` every four-component file is a
-    ``"components"`` fallback and an RGB-coded three-component file is decoded
-    as YCbCr: its colours are wrong and no fallback is reported.
-    ``info["colorspace"]`` names the mode in effect (when ``entropy`` was
-    prepared, the one it was prepared in; on a CPU device the one asked for,
-    and nothing native runs), ``info["colorspace_images"]`` counts the RGB /
-    CMYK / YCCK images decoded natively and not flagged."""
-    _check_entropy_on(entropy_on)
-    _check_progressive(progressive)
-    _check_restart(restart)
-    _check_sampling(sampling)
-    _check_colorspace(colorspace)
+    ``colorspace="auto"`` (default ``"ycbcr"``) decodes RGB-coded files and
+    four-component files sampled 1x1 (CMYK, YCCK), baseline or (with
+    ``progressive="native"``) progressive, with or without restart markers.
+    A four-component file with an Adobe transform other than 0 or 2 stays a
+    ``"components"`` fallback and any other four-component sampling is a
+    ``"sampling"`` one; four-component files take the one-lane kernel (or the
+    progressive one) under ``"gpu"``, ``"gpu_parallel"`` and
+    ``restart="intervals"`` alike.  Under the default every four-component
+    file is a ``"components"`` fallback and an RGB-coded three-component file
+    is decoded as YCbCr: its colours are wrong and no fallback is reported.
+    ``info["colorspace_images"]`` counts the RGB / CMYK / YCCK images decoded
+    natively and not flagged."""
+    _check("entropy_on", entropy_on)
+    opts = Options(progressive, restart, sampling, colorspace)
     device = torch.device(device)
     full = resize is None
     n = len(datas)
-    form = entropy_on if entropy is None else (entropy[0] if isinstance(entropy[0], str) else "host")
-    on_gpu = form in _DEVICE_FORMS
     if entropy is None:
+        form = entropy_on
         datas = [None if d is None else bytes(d) for d in datas]
     else:
-        # the form and the mode the entropy stage was prepared in decide
-        datas = entropy[1] if on_gpu else entropy[0]
-        progressive = ("native" if entropy[2].native_progressive else "fallback") if on_gpu else entropy[6]
-        if on_gpu:
-            restart = "intervals" if entropy[2].restart_intervals else "lane"
-            sampling = "native" if entropy[2].native_sampling else "fallback"
-            colorspace = "auto" if entropy[2].native_colorspace else "ycbcr"
-        else:
-            sampling = entropy[7]
-            colorspace = entropy[8]
-    native = progressive == "native"
-    samp = sampling == "native"
-    color = colorspace == "auto"
+        # the form and the options the entropy stage was prepared with decide
+        form, datas = entropy.form, entropy.datas
+        opts = entropy.options if form in _DEVICE_FORMS else replace(entropy.options, restart=restart)
+    on_gpu = form in _DEVICE_FORMS
     info = {"fallbacks": [], "entropy_s": 0.0, "h2d_s": 0.0, "idct_s": 0.0, "resize_s": 0.0, "kernel_s": 0.0,
-            "gpu_images": 0, "entropy_on": form, "progressive": progressive, "progressive_images": 0,
-            "restart": restart, "restart_images": 0, "sampling": sampling, "sampling_images": 0,
-            "colorspace": colorspace, "colorspace_images": 0}
+            "gpu_images": 0, "entropy_on": form, "progressive": opts.progressive, "progressive_images": 0,
+            "restart": opts.restart, "restart_images": 0, "sampling": opts.sampling, "sampling_images": 0,
+            "colorspace": opts.colorspace, "colorspace_images": 0}
     host = (lambda d: _pil_full(d)) if full else (lambda d: load_image_u8(d, resize, crop))
     if device.type != "cuda":
         # no GPU: every image through Pillow, nothing of the native path
@@ -582,26 +562,19 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
     C = _C()
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    packed = None
-    if on_gpu:
-        _, _, packed, info["pack_s"] = entropy if entropy is not None else entropy_batch(datas, threads, form,
-                                                                                         progressive, restart, sampling,
-                                                                                         colorspace)
-        status, hdr, offs, coef_elems = list(packed.status), packed.hdr, packed.offs, packed.coef_total
-    else:
-        _, status, hdr, coefs, offs, info["entropy_s"] = (entropy if entropy is not None else
-                                                          entropy_batch(datas, threads, "host", progressive,
-                                                                        sampling=sampling, colorspace=colorspace))[:6]
-        status = list(status)
-        coef_elems = coefs.numel()
+    if entropy is None:
+        entropy = entropy_batch(datas, threads, form, opts.progressive, opts.restart, opts.sampling, opts.colorspace)
+    info["pack_s" if on_gpu else "entropy_s"] = entropy.seconds
+    status, hdr, offs, coef_elems = list(entropy.status), entropy.hdr, entropy.offs, entropy.coef_elems
+    coefs, packed = entropy.coefs, entropy.packed
+    ws, hs = _header_column(hdr, 0), _header_column(hdr, 4)      # JpegHeader starts with int W, H
     geom = None
     if not full:
-        hv = hdr.numpy().view(np.int32)           # JpegHeader starts with int W, H
         seen: dict = {}                           # datasets repeat a few sizes: one evaluation per size
         rows = [(0, 0, 0, 0)] * n
         for i in range(n):
             if status[i] == 0:
-                wh = (int(hv[i, 0]), int(hv[i, 1]))
+                wh = (int(ws[i]), int(hs[i]))
                 g = seen.get(wh)
                 if g is None:
                     g = seen[wh] = resize_geometry(wh[0], wh[1], resize, crop)
@@ -655,25 +628,27 @@ def decode_batch(datas, device, resize: int | None = 256, crop: int | None = 224
                 imgs.append(None)
                 continue
             if status[i] != 0:
-                info["fallbacks"].append((i, _refusal(C, d, status[i], native, samp, color)))
+                info["fallbacks"].append((i, _refusal(C, d, status[i], opts)))
                 t = torch.from_numpy(host(d).copy()).to(device)
                 if full:
                     imgs.append(t)
                 else:
                     out[i].copy_(t)
             elif full:
-                h, w = int(hdr[i].numpy().view(np.int32)[1]), int(hdr[i].numpy().view(np.int32)[0])
+                h, w = int(hs[i]), int(ws[i])
                 o = plan.out_off[i]
                 imgs.append(out[o:o + h * w * 3].view(h, w, 3))
-        if native and n:
-            prog = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_PROGRESSIVE_OFFSET // 4]
-            info["progressive_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and prog[i])
-        if samp and n:
-            mode = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_MODE_OFFSET // 4]
-            info["sampling_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and mode[i] >= 3)
-        if color and n:
-            cs = hdr.numpy().view(np.int32)[:, C.JPEG_HEADER_COLORSPACE_OFFSET // 4]
-            info["colorspace_images"] = sum(1 for i in range(n) if status[i] == 0 and datas[i] is not None and cs[i] != 0)
+        if n:
+            # one pass over the header rows for the three counters: an option's images are those it is on
+            # for, that were decoded natively and not flagged, and whose header field says so (progressive
+            # is 0 / 1, mode 0..4, colorspace 0..3, never negative: "set" is ">= 1", modes 3 and 4 ">= 3")
+            taken = np.array([status[i] == 0 and datas[i] is not None for i in range(n)])
+            for key, on, offset, least in (
+                    ("progressive_images", opts.native_progressive, C.JPEG_HEADER_PROGRESSIVE_OFFSET, 1),
+                    ("sampling_images", opts.native_sampling, C.JPEG_HEADER_MODE_OFFSET, 3),
+                    ("colorspace_images", opts.native_colorspace, C.JPEG_HEADER_COLORSPACE_OFFSET, 1)):
+                if on:
+                    info[key] = int(np.count_nonzero(taken & (_header_column(hdr, offset) >= least)))
         # the result is complete when it is returned, whatever the batch held (the zero fill and
         # the fallbacks' copies too): a holder may hand it to a consumer on any other stream
         cur.synchronize()

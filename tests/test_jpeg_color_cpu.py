@@ -203,9 +203,9 @@ def test_host_batch_and_coefs_take_the_keyword():
         assert np.array_equal(coefs[offs[i]:offs[i] + h["total_coefs"]].numpy(), c)
     assert jpeg.entropy_coefs(ds)[0] == [7, 0, 1, 0, 7]
     ent = jpeg.entropy_batch(ds, 2, colorspace="auto")
-    assert list(ent[1]) == [0, 0, 1, 0, 0] and ent[7] == "fallback" and ent[8] == "auto"
-    assert list(jpeg.entropy_batch(ds, 2)[1]) == [7, 0, 1, 0, 7] and jpeg.entropy_batch(ds, 2)[8] == "ycbcr"
-    cs = ent[2].numpy().view(np.int32)[:, ops.JPEG_HEADER_COLORSPACE_OFFSET // 4].tolist()
+    assert list(ent.status) == [0, 0, 1, 0, 0] and ent.options.sampling == "fallback" and ent.options.colorspace == "auto"
+    assert list(jpeg.entropy_batch(ds, 2).status) == [7, 0, 1, 0, 7] and jpeg.entropy_batch(ds, 2).options.colorspace == "ycbcr"
+    cs = ent.hdr.numpy().view(np.int32)[:, ops.JPEG_HEADER_COLORSPACE_OFFSET // 4].tolist()
     assert cs == [CMYK, YCBCR, 0, RGB, YCCK]
 
 
@@ -217,7 +217,7 @@ def test_bindings_take_the_flag_last_and_the_packer_keeps_four_components_off_tw
     assert C.jpeg_parse(d)[:2] == (7, "components") and C.jpeg_parse(d, False, False, False)[:2] == (7, "components")
     st, reason, h = C.jpeg_parse(d, False, False, True)
     assert (st, reason, h["colorspace"], h["ncomp"]) == (0, "ok", CMYK, 4)
-    assert ops.jpeg_parse_colorspace(d)[0] == 0 and C.jpeg_parse(d, native_colorspace=True)[0] == 0
+    assert ops.jpeg_parse(d, native_colorspace=True)[0] == 0 and C.jpeg_parse(d, native_colorspace=True)[0] == 0
     assert list(ops.jpeg_entropy_batch([d], 1, False, False, True)[0]) == [0]
     assert list(ops.jpeg_entropy_batch([d], 1)[0]) == [7]
     # a four-component file takes the one-lane kernel in every layout, an RGB-coded one goes with its YCbCr twins

@@ -142,7 +142,7 @@ def test_a_prepared_entropy_stage_decides_the_mode(form):
     datas = list(image_batch())
     host, _ = jpeg.decode_batch(datas, DEV, entropy_on="host")
     ent = jpeg.entropy_batch(datas, 8, form, restart="intervals")
-    assert ent[2].restart_intervals is True and ent[2].n_rst == N_RST
+    assert ent.packed.restart_intervals is True and ent.packed.n_rst == N_RST
     gpu, ginfo = jpeg.decode_batch(datas, DEV, entropy=ent)                       # called with the default
     assert ginfo["restart"] == "intervals" and ginfo["restart_images"] == N_ACCEPTED and ginfo["entropy_on"] == form
     assert torch.equal(gpu, host)

@@ -107,8 +107,8 @@ def test_host_batch_and_coefs_take_the_keyword():
         assert np.array_equal(coefs[offs[i]:offs[i] + h["total_coefs"]].numpy(), c)
     assert jpeg.entropy_coefs(ds)[0] == [9, 0, 1, 9]
     ent = jpeg.entropy_batch(ds, 2, sampling="native")
-    assert list(ent[1]) == [0, 0, 1, 0] and ent[7] == "native"
-    assert list(jpeg.entropy_batch(ds, 2)[1]) == [9, 0, 1, 9]
+    assert list(ent.status) == [0, 0, 1, 0] and ent.options.sampling == "native"
+    assert list(jpeg.entropy_batch(ds, 2).status) == [9, 0, 1, 9]
 
 
 def test_cpu_device_runs_nothing_native(tmp_path):
@@ -157,8 +157,10 @@ def test_both_parsers_take_the_flag_and_keep_their_defaults():
         st, reason, h = parse(d, False, True)
         assert (st, reason, h["mode"]) == (0, "ok", 4)
         assert parse(d, native_sampling=True)[0] == 0
-    assert list(inspect.signature(ops.jpeg_parse).parameters) == ["data", "native_progressive", "native_sampling"]
+    assert list(inspect.signature(ops.jpeg_parse).parameters) == ["data", "native_progressive", "native_sampling",
+                                                                  "native_colorspace"]
     assert inspect.signature(ops.jpeg_parse).parameters["native_sampling"].default is False
+    assert inspect.signature(ops.jpeg_parse).parameters["native_colorspace"].default is False
     for fn in (jpeg.parse, jpeg.entropy_decode, jpeg.entropy_batch, jpeg.entropy_coefs, jpeg.decode_batch):
         assert inspect.signature(fn).parameters["sampling"].default == "fallback", fn.__name__
     # the packer takes it too, remembers it, and lays such a file out like any other of its kind
