@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from idunno.models import HipRunner
 from idunno.models import packed as P
 from idunno.models import reference as ref
 
@@ -23,7 +24,7 @@ def ops():
 
 
 def _runner(prog, dtype):
-    r = P.HipRunner(prog, DEV)
+    r = HipRunner(prog, DEV)
     if dtype == "fp32":
         assert r.split and r._split_ok()
     return r

@@ -247,7 +247,20 @@ def test_run_packed_resident_window_matches_copy():
         assert np.array_equal(got[:, 1].cpu().numpy().view(np.float32), want_prob)
         assert r.has_window(src.data, 48, packed=packed[:48])
     assert len(r._graphs) == ngraphs
-    assert src.get(195, 205).shape[0] == 11         # past the resident range: generated per request
+    # capture_window again with the same arguments: the cached graph, and a closure
+    # that keeps the packed buffer the graph writes into alive like the first one
+    buf = packed[:48]
+    start1, first = r.capture_window(src.data, 48, packed=buf)
+    start2, again = r.capture_window(src.data, 48, packed=buf)
+    assert start2 is start1 and len(r._graphs) == ngraphs
+    assert any(k is buf for k in again._keep[1])
+    start1.fill_(40)
+    want = [t.clone() for t in first()] + [buf.clone()]
+    buf.zero_()
+    got = [t.clone() for t in again()] + [buf.clone()]
+    torch.cuda.synchronize()
+    assert all(torch.equal(g, w) for g, w in zip(got, want))
+    assert src.get(195, 205).shape[0] == 11       # past the resident range: generated per request
     # a view of any other tensor (an SDFS shard) keeps the static-input graph
     other = src.data.clone()
     n0 = len(r._graphs)

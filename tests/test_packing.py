@@ -31,6 +31,36 @@ def test_pack_unpack_roundtrip_small_and_big():
     assert packed.pack_conv_weight(torch.randn(64, 3, 11, 11))[0].shape == (64, 11 * 64)
 
 
+@pytest.mark.parametrize("name", ["alexnet", "resnet18"])
+def test_program_to_keeps_every_conv_field(name):
+    """fp32 programs populate wino, p3, sw, sp3 and fs* between them: a moved
+    program's convs equal the source's in every dataclass field."""
+    import dataclasses
+
+    p = packed.build_program(name, seed=0, randomize_bn=True, dtype="fp32")
+    q = p.to("cpu")
+    src, moved = list(p.all_convs()), list(q.all_convs())
+    assert len(src) == len(moved) and (q.name, q.kind, q.num_classes, q.dtype) == (name, p.kind, 1000, "fp32")
+    seen = set()
+    for a, b in zip(src, moved):
+        for f in dataclasses.fields(packed.Conv):
+            x, y = getattr(a, f.name), getattr(b, f.name)
+            if isinstance(x, torch.Tensor):
+                seen.add(f.name)
+                assert isinstance(y, torch.Tensor) and x.dtype == y.dtype and torch.equal(x, y), f.name
+            else:
+                assert type(x) is type(y) and x == y, f.name
+    assert seen == {"w", "b", "wino", "p3", "sw", "sp3", "fs", "fs_bias", "fs_psum"}
+
+
+def test_packed_holds_no_runner():
+    """The runner lives in models/runner.py alone: packed.py has no alias of it."""
+    from idunno import models
+
+    assert models.HipRunner is models.runner.HipRunner
+    assert not hasattr(packed, "HipRunner")
+
+
 def test_flops():
     p = packed.build_program("resnet18")
     assert abs(packed.program_flops(p) / 1e9 - 3.63) < 0.02

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from idunno.models import HipRunner
 from idunno.models import packed as P
 
 DEV = "cuda"
@@ -499,7 +500,7 @@ def test_model_split_vs_fp64_oracle(ops, name, B):
 
     m = ref.build(name, seed=0)
     prog = P.compile_model(m, name, "fp32")
-    r = P.HipRunner(prog)
+    r = HipRunner(prog)
     assert r.split and r._split_ok()
     img = ops.synth_images(0, 0, B, DEV)
     got = r.logits(img).double().cpu()
@@ -573,7 +574,7 @@ def test_split_activations_past_fp16_range_match_fp64(ops):
     with torch.no_grad():
         m.conv1.weight *= 1e5
     prog = P.compile_model(m, "resnet18", "fp32")
-    r = P.HipRunner(prog)
+    r = HipRunner(prog)
     assert r.split and r._split_ok()
     img = ops.synth_images(4, 0, 4, DEV)
     with torch.no_grad():
@@ -648,7 +649,7 @@ def test_resnet18_fused_downsample_same_logits(ops):
     from idunno.models import reference as ref
 
     m = ref.build("resnet18", seed=2, randomize_bn=True)
-    r = P.HipRunner(P.compile_model(m, "resnet18", "fp32"))
+    r = HipRunner(P.compile_model(m, "resnet18", "fp32"))
     img = ops.synth_images(7, 0, 24, DEV)
     r.fuse_down = True
     assert all(r._dual_ok(b) for b in r.p.blocks if b.down is not None)

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from idunno.models import HipRunner
 from idunno.models import packed as P
 
 DEV = "cuda"
@@ -240,7 +241,7 @@ def _stem_out(r, img):
 @pytest.mark.gpu
 def test_resnet18_tail_fusion_same_logits_and_oracle(ops, resnet18):
     prog, img, want = resnet18
-    r = P.HipRunner(prog)
+    r = HipRunner(prog)
     assert r.split and r._split_ok()
     r.fuse_down_tail = 0
     plain = r.logits(img).double()
@@ -271,7 +272,7 @@ def test_resnet18_tail_fusion_same_logits_and_oracle(ops, resnet18):
 @pytest.mark.gpu
 def test_resnet18_tail_fusion_graph_replay_is_eager_bitwise(ops, resnet18):
     prog, img, _ = resnet18
-    r = P.HipRunner(prog)
+    r = HipRunner(prog)
     r.fuse_down_tail = 2
     c0, p0 = r.forward(img)
     _start, run = r.capture_window(img, 4)
@@ -284,3 +285,36 @@ def test_resnet18_tail_fusion_graph_replay_is_eager_bitwise(ops, resnet18):
     k_off = r._capture_key(4)
     r.fuse_down_tail = 2
     assert r._capture_key(4) != k_off
+
+
+def _other(v):
+    """A value of the switch's own kind that differs from ``v`` (also after int())."""
+    if isinstance(v, bool):
+        return not v
+    return 2 if v is None else v + 1
+
+
+@pytest.mark.gpu
+def test_every_declared_graph_switch_is_in_the_capture_key(ops, resnet18):
+    r = HipRunner(resnet18[0])
+    assert "astem_form" in r.GRAPH_SWITCHES and "fuse_down_tail" in r.GRAPH_SWITCHES
+    # a public attribute the constructor sets is a declared switch unless it is named here:
+    # a switch added later cannot stay out of the key unnoticed
+    not_switches = {"ops", "device", "p", "graph_pool", "overflow_fallback", "overflow_reruns", "direct_launch"}
+    public = {k for k in vars(r) if not k.startswith("_")}
+    assert public - not_switches == set(r.GRAPH_SWITCHES)
+    k0 = r._capture_key(4)
+    for name in r.GRAPH_SWITCHES:
+        was = getattr(r, name)
+        setattr(r, name, _other(was))
+        assert r._capture_key(4) != k0, name
+        setattr(r, name, was)
+        assert r._capture_key(4) == k0, name
+
+
+@pytest.mark.gpu
+def test_astem_form_is_in_the_capture_key(ops):
+    r = HipRunner(P.build_program("alexnet", seed=0))
+    k0 = r._capture_key(4)
+    r.astem_form = 0
+    assert r._capture_key(4) != k0
