@@ -27,7 +27,11 @@ class ClusterConfig:
 
     # -- inference ------------------------------------------------------------
     batch_size: dict = field(default_factory=lambda: {"alexnet": 500, "resnet18": 400,
-                                                      "resnet50": 1024, "resnet34": 400})
+                                                      "resnet50": 1024, "resnet34": 400,
+                                                      # the rest of the ResNet family: the reference's query size
+                                                      "resnet101": 400, "resnet152": 400, "resnext50_32x4d": 400,
+                                                      "resnext101_32x8d": 400, "wide_resnet50_2": 400,
+                                                      "wide_resnet101_2": 400})
     worker_budget: int = 8                   # reference RATE_FACTOR (:44) -> GPUs shared by jobs
     max_chunk: int = 1024                    # largest per-worker batch (HBM is not the limit)
     dataset_size: int = 10000                # reference dataset: 10,000 images (report p.1)

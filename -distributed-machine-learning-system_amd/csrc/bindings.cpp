@@ -40,6 +40,11 @@ Tensor linear_split(Tensor x, Tensor w, Tensor bias, double acc_scale, bool relu
 Tensor split_from_f32(Tensor x);
 Tensor f32_from_split(Tensor x);
 Tensor maxpool2d_split(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out);
+// bind_conv_grouped.cpp
+Tensor conv3x3_grouped(Tensor x, Tensor w, Tensor bias, int64_t groups, int64_t stride, bool relu);
+Tensor conv3x3_grouped_split(Tensor x, Tensor w, Tensor bias, double acc_scale, int64_t groups, int64_t stride,
+                             bool relu);
+bool conv3x3_grouped_ok(int64_t C, int64_t groups, int64_t stride);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -157,6 +162,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("img"), py::arg("w"), py::arg("bias"), py::arg("psum"), py::arg("acc_scale"),
         py::arg("start") = py::none(), py::arg("batch") = -1, py::arg("start_offset") = 0, py::arg("window") = -1,
         py::arg("sub") = 0, py::arg("form") = -1);
+  m.def("conv3x3_grouped", &conv3x3_grouped, "grouped 3x3 pad-1 conv + bias (+relu), fp16 NHWC", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("groups"), py::arg("stride"), py::arg("relu"));
+  m.def("conv3x3_grouped_split", &conv3x3_grouped_split,
+        "grouped 3x3 pad-1 conv + bias (+relu) on split-fp16 operands (fp32-accurate, range-guarded)", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("acc_scale"), py::arg("groups"), py::arg("stride"), py::arg("relu"));
+  m.def("conv3x3_grouped_ok", &conv3x3_grouped_ok, "whether the grouped 3x3 kernel takes (C, groups, stride)");
   m.def("pick_tile_split", &pick_tile_split, "split conv tile heuristic for (M, Cout)");
   m.def("conv2d_nhwc_f32", &conv2d_nhwc_f32, "fp32 implicit-GEMM conv on f32 MFMA + bias (+res) (+relu)",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("res"), py::arg("KH"), py::arg("KW"), py::arg("stride"),

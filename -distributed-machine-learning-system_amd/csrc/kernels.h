@@ -204,6 +204,12 @@ bool conv3x3_c64_supported(int C, int Cout);
 void conv3x3_c64_launch(const half_t* x, const half_t* w, const float* bias, const half_t* res, half_t* y,
                         const void* zero, int B, int H, int W, int relu, hipStream_t st);
 int conv_glds_pick(int M, int Cout);
+// grouped 3x3 pad-1 conv, stride 1 or 2, + bias (+ReLU) (conv3x3_grouped.hip): C % 32 == 0, Cg = C / groups in
+// {4, 8, 16, 32, 64}; x / y NHWC fp16 and w [C][9 CB], or with `split` the split layout and w [C][2 * 9 CB]
+// (CB = max(16, Cg), grouped_math.h).  False: unsupported shape or a grid past int32.
+bool conv3x3_grouped_supported(int C, int groups, int stride);
+bool conv3x3_grouped_launch(const half_t* x, const half_t* w, const float* bias, half_t* y, int B, int H, int W, int C,
+                            int groups, int stride, int relu, bool split, float acc_scale, int* ovf, hipStream_t st);
 // split-fp16 (fp32-accurate) fused stem, exact-u8 form: w = [2][64][7*32] hi/lo of
 // w * s_c (pre-scaled by 1/acc_scale), bias = folded bias + full sum of w * c_c,
 // psum = [8][8][64] 2D prefix sums of w * c_c over (kh, kw); y = split [B][Hp][Wp][128]

@@ -147,7 +147,8 @@ def deeplearning(filename: str, modelname: str, start_image: int, end_image: int
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="one-process inference over test_<i>.JPEG (or synthetic) images")
-    ap.add_argument("model", help="alexnet | resnet18 | resnet | resnet34 | resnet50")
+    ap.add_argument("model", help="alexnet | resnet18 | resnet | resnet34 | resnet50 | resnet101 | resnet152 | resnext50_32x4d | "
+                                  "resnext101_32x8d | wide_resnet50_2 | wide_resnet101_2")
     ap.add_argument("start", type=int)
     ap.add_argument("end", type=int)
     ap.add_argument("--dir", default=None, help="image directory (default: ./<model>, else synthetic)")

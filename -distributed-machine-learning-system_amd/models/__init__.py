@@ -1,4 +1,5 @@
-"""Model families of the reference (AlexNet, ResNet18) plus ResNet34/50.
+"""Model families of the reference (AlexNet, ResNet18) plus the rest of
+torchvision v0.10's ResNet family (ResNet34-152, ResNeXt, Wide ResNet).
 
 ``reference``  plain-PyTorch fp32 oracle modules (torchvision-compatible keys)
 ``packed``     BN-folded, MFMA-packed inference programs + their fp32 CPU emulator

@@ -1,8 +1,11 @@
 """Trained checkpoints for the reference architectures.
 
 The module trees of ``models.reference`` use torchvision's parameter names, so
-a ``state_dict`` saved from torchvision's ``resnet18`` / ``resnet50`` /
-``alexnet`` (or from ``reference.build``) loads strictly:
+a ``state_dict`` saved from torchvision's ``alexnet`` or any member of its
+v0.10 ResNet family (``resnet18/34/50/101/152``, ``resnext50_32x4d``,
+``resnext101_32x8d``, ``wide_resnet50_2``, ``wide_resnet101_2``; a grouped
+``conv2.weight`` is ``[width, width // groups, 3, 3]``), or from
+``reference.build``, loads strictly:
 
     state = load_state("resnet18.pth")            # or .safetensors
     m = model_from_state("resnet18", state)       # nn.Module, eval mode
@@ -111,7 +114,11 @@ def model_from_state(name: str, state: dict) -> nn.Module:
         if extra:
             parts.append(f"unexpected keys: {_few(extra)}")
         raise ValueError(f"{name}: checkpoint does not match the architecture; " + "; ".join(parts))
-    shape = [f"{k} {tuple(state[k].shape)} != {tuple(v.shape)}" for k, v in want.items() if state[k].shape != v.shape]
+    # conv / linear weights first: the per-channel vectors that differ with them (BN, bias) say nothing more,
+    # and a ResNeXt checkpoint offered as a ResNet should name the grouped conv2 among the first few
+    shape = [f"{k} {tuple(state[k].shape)} != {tuple(v.shape)}"
+             for first in (True, False) for k, v in want.items()
+             if state[k].shape != v.shape and (v.dim() >= 2) == first]
     if shape:
         raise ValueError(f"{name}: shape mismatch: {_few(shape)}")
     bad = [k for k in want if not state[k].is_floating_point()]

@@ -12,6 +12,8 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
   * fp32 programs (dtype "fp32", the reference's precision) keep fp32 weights;
     their 3x3/stride-1 convs also carry the Winograd F(2x2,3x3) filter
     transform U = G g G^T [16, Cout, Cin] (conv_wino_f32.hip)
+  * grouped 3x3 convs (ResNeXt) -> channel-block-local [Cout, 9 * CB] weights
+    (pack_grouped_weight / pack_grouped_split_weight), never a dense expansion
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -54,6 +56,10 @@ class Conv:
     fs_bias: torch.Tensor | None = None  # ... its bias (with the normalisation shift folded in)
     fs_psum: torch.Tensor | None = None  # ... its border-correction prefix sums [8, 8, 64]
     fs_scale: float = 1.0              # ... its accumulator scale 2^-e
+    # grouped 3x3 conv (ResNeXt): ``w`` is the block-local fp16 form (pack_grouped_weight) in fp16
+    # programs and the plain fp32 [Cout, Cin/groups, 3, 3] weight in fp32 programs, whose ``sw`` is
+    # the block-local split form (pack_grouped_split_weight); cin / cout stay the full widths
+    groups: int = 1
 
     def to(self, device):
         vals = {f.name: getattr(self, f.name) for f in fields(self)}
@@ -61,7 +67,7 @@ class Conv:
 
     @property
     def flops_per_out_pixel(self) -> int:
-        return 2 * self.cin * self.kh * self.kw * self.cout
+        return 2 * self.cin * self.kh * self.kw * self.cout // self.groups
 
 
 @dataclass
@@ -190,7 +196,10 @@ def pack3_eligible(cin: int, kw: int, stride: int = 2, dtype: str = "fp32") -> b
 
 
 def unpack_conv_weight(c: Conv) -> torch.Tensor:
-    """Inverse of pack_conv_weight -> fp32 [Cout, Cin, KH, KW]."""
+    """Inverse of pack_conv_weight -> fp32 [Cout, Cin, KH, KW] (a grouped conv:
+    [Cout, Cin / groups, 3, 3], its fp32 copy in fp32 programs)."""
+    if c.groups > 1:
+        return c.w.float().contiguous() if c.w.dim() == 4 else unpack_grouped_weight(c)
     w = c.w.float()
     if c.small:
         tpr = 4 if c.w.dtype == torch.float32 else 8        # taps per K row (see pack_conv_weight)
@@ -374,6 +383,99 @@ def unpack_split_weight(c: "Conv") -> torch.Tensor:
     return w.permute(0, 3, 1, 2).float().contiguous()
 
 
+# ---------------------------------------------------------------------------
+# grouped 3x3 convs (ResNeXt): channel-block-local weights (conv3x3_grouped.hip)
+# ---------------------------------------------------------------------------
+# With Cg = Cin / groups = Cout / groups and CB = max(16, Cg), output channels
+# [CB j, CB j + CB) read input channels of the same range only (groups are
+# contiguous and Cg divides CB): per block a small dense [CB outputs, 9 taps, CB
+# inputs] weight.  For Cg < 16 the slots outside an output's own group are zero
+# (75 % zeros at Cg 4, 50 % at Cg 8; the kernel is bandwidth-bound).
+
+GROUPED_CG = (4, 8, 16, 32, 64)
+
+
+def grouped_block(cg: int) -> int:
+    """Channel block CB of a grouped conv with ``cg`` channels per group."""
+    if cg not in GROUPED_CG:
+        raise ValueError(f"grouped conv: {cg} channels per group unsupported (need one of {GROUPED_CG})")
+    return max(16, cg)
+
+
+def _grouped_shape(w: torch.Tensor, groups: int) -> tuple[int, int, int]:
+    """(Cout, Cg, CB) of a grouped 3x3 weight [Cout, Cg, 3, 3], checked."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"grouped conv weights must be [Cout, Cin/groups, 3, 3], got {tuple(w.shape)}")
+    cout, cg = w.shape[0], w.shape[1]
+    if groups < 2 or cout % groups or cout // groups != cg:
+        raise ValueError(f"grouped conv: Cout={cout}, groups={groups} and {cg} input channels per group do not "
+                         "describe a conv with Cin = Cout")
+    if cg not in GROUPED_CG:
+        raise ValueError(f"grouped conv: Cout={cout} / groups={groups} = {cg} channels per group unsupported "
+                         f"(need one of {GROUPED_CG})")
+    return cout, cg, grouped_block(cg)
+
+
+def _grouped_rows(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """[Cout, Cg, 3, 3] -> block-local rows [Cout, 9 * CB] in w's dtype."""
+    cout, cg, cb = _grouped_shape(w, groups)
+    rows = torch.zeros(cout, 9, cb, dtype=w.dtype)
+    slot = (torch.arange(cout) % cb) // cg * cg             # first slot of each output's own group
+    idx = slot.view(-1, 1) + torch.arange(cg).view(1, -1)   # [Cout, Cg]
+    rows.scatter_(2, idx.view(cout, 1, cg).expand(cout, 9, cg), w.permute(0, 2, 3, 1).reshape(cout, 9, cg))
+    return rows.reshape(cout, 9 * cb)
+
+
+def pack_grouped_weight(w: torch.Tensor, groups: int, dtype: str = "fp16") -> torch.Tensor:
+    """[Cout, Cg, 3, 3] fp32/fp64 -> block-local fp16 weights [Cout, 9 * CB].
+
+    Row ``co`` is the K axis of the block's GEMM: k = tap * CB + ci with
+    tap = 3 kh + kw and ci the input channel within co's channel block
+    (input channel CB * (co // CB) + ci); slot ci holds w[co, ci % Cg, kh, kw]
+    where ci // Cg == (co % CB) // Cg, zero elsewhere.  The kernel reads it in
+    K-steps of 32 (CB 16: two taps a step, the tenth tap absent)."""
+    if dtype != "fp16":
+        raise ValueError("grouped weights are fp16 (fp32 programs carry pack_grouped_split_weight)")
+    return _grouped_rows(w.float(), groups).half().contiguous()
+
+
+def pack_grouped_split_weight(w: torch.Tensor, groups: int) -> tuple[torch.Tensor, float]:
+    """[Cout, Cg, 3, 3] -> (split block-local weights [Cout, 2 * 9 * CB] half,
+    acc_scale): each row is [hi 9 CB | lo 9 CB] of pack_grouped_weight's row,
+    scaled by 2^e (one exponent per conv) exactly as pack_split_weight does."""
+    e = _split_scale(w)
+    hi, lo = _hi_lo(_grouped_rows(w.double(), groups) * (2.0 ** e))
+    return torch.cat([hi, lo], dim=1).contiguous(), 2.0 ** -e
+
+
+def unpack_grouped_weight(c: "Conv") -> torch.Tensor:
+    """Inverse of pack_grouped_weight (``c.w`` fp16 rows) and of
+    pack_grouped_split_weight (``c.sw``, preferred when present: hi + lo,
+    unscaled) -> fp32 [Cout, Cg, 3, 3]."""
+    cg = c.cin // c.groups
+    cb = grouped_block(cg)
+    if c.sw is not None:
+        rows = (c.sw[:, :9 * cb].double() + c.sw[:, 9 * cb:].double()) * c.s_scale
+    else:
+        rows = c.w.double()
+    slot = (torch.arange(c.cout, device=rows.device) % cb) // cg * cg
+    idx = slot.view(-1, 1) + torch.arange(cg, device=rows.device).view(1, -1)
+    w = rows.reshape(c.cout, 9, cb).gather(2, idx.view(c.cout, 1, cg).expand(c.cout, 9, cg))
+    return w.reshape(c.cout, 3, 3, cg).permute(0, 3, 1, 2).float().contiguous()
+
+
+def expand_grouped_weight(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """[Cout, Cg, 3, 3] -> the dense block-diagonal [Cout, Cin, 3, 3] (w's dtype)
+    that computes the same conv without ``groups``: groups x the weights."""
+    cout, cg = w.shape[0], w.shape[1]
+    if cout % groups or cout // groups != cg:
+        raise ValueError(f"grouped conv: Cout={cout}, groups={groups}, {cg} channels per group")
+    dense = torch.zeros(cout, cout, *w.shape[2:], dtype=w.dtype, device=w.device)
+    for g in range(groups):
+        dense[g * cg:(g + 1) * cg, g * cg:(g + 1) * cg] = w[g * cg:(g + 1) * cg]
+    return dense
+
+
 # Winograd F(2x2, 3x3) filter transform (Lavin & Gray): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
@@ -396,6 +498,20 @@ def make_conv(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, relu: bool, dtype: str
     cin, cout, (kh, kw), stride, pad = conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride[0], \
         conv.padding[0]
     f32 = dtype == "fp32"
+    if conv.groups > 1:
+        # block-local weights only: never pack_conv_weight (Cin / groups is no multiple of 64) and no
+        # dense expansion here (resnext101_32x8d's would be 1.4 GB in fp32; runner.py builds one lazily
+        # per conv where a path needs it)
+        if (kh, kw, pad) != (3, 3, 1) or stride not in (1, 2) or cin != cout:
+            raise ValueError(f"grouped convs are 3x3 pad-1 stride-1/2 with Cin = Cout, got {tuple(conv.weight.shape)} "
+                             f"stride {stride} pad {pad} groups {conv.groups}")
+        if dtype not in DTYPES:
+            raise ValueError(f"dtype must be one of {DTYPES}, got {dtype!r}")
+        c = Conv(w=w.contiguous() if f32 else pack_grouped_weight(w, conv.groups), b=b.contiguous(), cin=cin,
+                 cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, relu=relu, groups=conv.groups)
+        if f32:
+            c.sw, c.s_scale = pack_grouped_split_weight(w64, conv.groups)
+        return c
     pw, small = pack_conv_weight(w, dtype)
     c = Conv(w=pw, b=b.contiguous(), cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, relu=relu, small=small)
     if f32 and split_eligible(cin, cout):
@@ -495,7 +611,7 @@ def build_program(name: str, seed: int = 0, randomize_bn: bool = False, dtype: s
 # ---------------------------------------------------------------------------
 
 def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torch.Tensor:
-    y = F.conv2d(x, unpack_conv_weight(c).to(x.device), c.b.to(x.device), c.stride, c.pad)
+    y = F.conv2d(x, unpack_conv_weight(c).to(x.device), c.b.to(x.device), c.stride, c.pad, groups=c.groups)
     if res is not None:
         y = y + res
     return F.relu(y) if c.relu else y

@@ -22,15 +22,17 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-def _conv(cin, cout, k, s=1, p=0):
-    return nn.Conv2d(cin, cout, k, stride=s, padding=p, bias=False)
+def _conv(cin, cout, k, s=1, p=0, groups=1):
+    return nn.Conv2d(cin, cout, k, stride=s, padding=p, groups=groups, bias=False)
 
 
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin, width, stride=1, downsample=None):
+    def __init__(self, cin, width, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
+        if groups != 1 or base_width != 64:
+            raise ValueError("BasicBlock only supports groups=1 and base_width=64")
         self.conv1 = _conv(cin, width, 3, stride, 1)
         self.bn1 = nn.BatchNorm2d(width)
         self.conv2 = _conv(width, width, 3, 1, 1)
@@ -46,18 +48,23 @@ class BasicBlock(nn.Module):
 
 
 class Bottleneck(nn.Module):
-    """ResNet v1.5 bottleneck: the stride sits on the 3x3 conv."""
+    """ResNet v1.5 bottleneck: the stride sits on the 3x3 conv.  ``groups`` and
+    ``base_width`` are torchvision's: the inner width is
+    ``int(planes * base_width / 64) * groups`` (ResNeXt: 32 groups of 4 or 8
+    channels per 64 planes; Wide ResNet: base_width 128), conv2 is grouped, and
+    the block's output stays ``planes * 4``."""
 
     expansion = 4
 
-    def __init__(self, cin, width, stride=1, downsample=None):
+    def __init__(self, cin, planes, stride=1, downsample=None, groups=1, base_width=64):
         super().__init__()
+        width = int(planes * base_width / 64) * groups
         self.conv1 = _conv(cin, width, 1)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = _conv(width, width, 3, stride, 1)
+        self.conv2 = _conv(width, width, 3, stride, 1, groups)
         self.bn2 = nn.BatchNorm2d(width)
-        self.conv3 = _conv(width, width * 4, 1)
-        self.bn3 = nn.BatchNorm2d(width * 4)
+        self.conv3 = _conv(width, planes * 4, 1)
+        self.bn3 = nn.BatchNorm2d(planes * 4)
         self.downsample = downsample
         self.stride = stride
 
@@ -70,8 +77,9 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, block, layers, num_classes=1000):
+    def __init__(self, block, layers, num_classes=1000, groups=1, width_per_group=64):
         super().__init__()
+        self.groups, self.base_width = groups, width_per_group
         self.conv1 = _conv(3, 64, 7, 2, 3)
         self.bn1 = nn.BatchNorm2d(64)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
@@ -85,7 +93,7 @@ class ResNet(nn.Module):
                 if j == 0 and (s != 1 or cin != width * block.expansion):
                     ds = nn.Sequential(_conv(cin, width * block.expansion, 1, s),
                                        nn.BatchNorm2d(width * block.expansion))
-                blocks.append(block(cin, width, s, ds))
+                blocks.append(block(cin, width, s, ds, groups, width_per_group))
                 cin = width * block.expansion
             setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
         self.avgpool = nn.AdaptiveAvgPool2d(1)
@@ -137,11 +145,39 @@ def resnet50(num_classes=1000):
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes)
 
 
+def resnet101(num_classes=1000):
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes)
+
+
+def resnet152(num_classes=1000):
+    return ResNet(Bottleneck, [3, 8, 36, 3], num_classes)
+
+
+def resnext50_32x4d(num_classes=1000):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, groups=32, width_per_group=4)
+
+
+def resnext101_32x8d(num_classes=1000):
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes, groups=32, width_per_group=8)
+
+
+def wide_resnet50_2(num_classes=1000):
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, width_per_group=128)
+
+
+def wide_resnet101_2(num_classes=1000):
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes, width_per_group=128)
+
+
 def alexnet(num_classes=1000):
     return AlexNet(num_classes)
 
 
-BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet}
+# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet
+BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet,
+            "resnet101": resnet101, "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d,
+            "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
+            "wide_resnet101_2": wide_resnet101_2}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -196,7 +232,9 @@ def build(name: str, seed: int = 0, randomize_bn: bool = False) -> nn.Module:
 
 
 ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18",
-           "resnet-50": "resnet50", "alex": "alexnet"}
+           "resnet-50": "resnet50", "alex": "alexnet", "resnet-101": "resnet101", "resnet-152": "resnet152",
+           "resnext50": "resnext50_32x4d", "resnext101": "resnext101_32x8d",
+           "wide_resnet50": "wide_resnet50_2", "wide_resnet101": "wide_resnet101_2"}
 
 
 def canonical(name: str) -> str:

@@ -13,6 +13,7 @@ __all__ = [
     "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "softmax_topk", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
+    "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_ok",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -68,6 +69,26 @@ def conv2d_split_tail_ok(b: int, ho: int, wo: int, c: int, cx: int, cout: int, m
     arm); 3: the rule, but not where the band kernel is the unfused default
     (W 28: the other arm of the layer-2 A/B); 0: never."""
     return bool(load().conv2d_split_tail_ok(b, ho, wo, c, cx, cout, mode))
+
+
+def conv3x3_grouped(x, w, bias, groups: int, stride: int, relu: bool):
+    """Grouped 3x3 pad-1 conv (stride 1 or 2) + bias (+ReLU) on NHWC fp16
+    [B, H, W, C] (conv3x3_grouped.hip; f32 accumulation).  C % 32 == 0 and
+    C / groups in {4, 8, 16, 32, 64}; ``w`` = models.packed.pack_grouped_weight
+    ([C, 9 * CB] block-local fp16)."""
+    return load().conv3x3_grouped(x, w, bias, int(groups), int(stride), bool(relu))
+
+
+def conv3x3_grouped_split(x, w, bias, acc_scale: float, groups: int, stride: int, relu: bool):
+    """The same conv, fp32-accurate, on split-fp16 activations [B, H, W, 2C] and
+    weights (models.packed.pack_grouped_split_weight: [C, 2 * 9 * CB],
+    ``acc_scale``): hi*hi + hi*lo + lo*hi in f32; split output, range-guarded."""
+    return load().conv3x3_grouped_split(x, w, bias, float(acc_scale), int(groups), int(stride), bool(relu))
+
+
+def conv3x3_grouped_ok(c: int, groups: int, stride: int) -> bool:
+    """Whether the grouped 3x3 kernel takes ``c`` channels in ``groups`` groups at ``stride``."""
+    return bool(load().conv3x3_grouped_ok(int(c), int(groups), int(stride)))
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,

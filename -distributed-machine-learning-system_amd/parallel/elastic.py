@@ -51,7 +51,8 @@ import torch.distributed as dist
 
 log = logging.getLogger("idunno.elastic")
 
-MODEL_IDS = {"alexnet": 0, "resnet18": 1, "resnet50": 2, "resnet34": 3}
+MODEL_IDS = {"alexnet": 0, "resnet18": 1, "resnet50": 2, "resnet34": 3, "resnet101": 4, "resnet152": 5,
+             "resnext50_32x4d": 6, "resnext101_32x8d": 7, "wide_resnet50_2": 8, "wide_resnet101_2": 9}
 MODEL_NAMES = {v: k for k, v in MODEL_IDS.items()}
 HDR_ROWS = 2        # (compute_us, model_id), (n_images, tag) at the end of every send buffer
 

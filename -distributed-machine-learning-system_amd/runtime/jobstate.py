@@ -40,7 +40,10 @@ from ..utils import racecheck
 
 WINDOW_S = 30.0  # reference SLIDING_WINDOW_SECONDS * SLIDING_WINDOW_FACTOR (10 * 3)
 
-DEFAULT_BATCHSIZE = {"resnet18": 400, "alexnet": 500, "resnet50": 1024, "resnet34": 400}
+DEFAULT_BATCHSIZE = {"resnet18": 400, "alexnet": 500, "resnet50": 1024, "resnet34": 400,
+                     # the rest of the ResNet family at the reference's query size
+                     "resnet101": 400, "resnet152": 400, "resnext50_32x4d": 400, "resnext101_32x8d": 400,
+                     "wide_resnet50_2": 400, "wide_resnet101_2": 400}
 
 
 def class_names(n: int = 1000, path: str | None = None) -> list[str]:

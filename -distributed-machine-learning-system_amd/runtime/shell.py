@@ -24,7 +24,7 @@ MENU = """\
 10.ls sdfsfilename: list all nodes where this file is currently being stored
 11.store: list all files currently being stored at this node
 12.get-versions sdfsfilename num-versions localfilename: last num-versions versions, newest first, delimited
-13.inference <start> <end> <model>: submit queries (model: alexnet | resnet18 | resnet | resnet50)
+13.inference <start> <end> <model>: submit queries (model: alexnet | resnet18 | resnet | resnet34/50/101/152 | resnext50_32x4d | resnext101_32x8d | wide_resnet50_2 | wide_resnet101_2)
 c1 query rate and finished inferences for each model
 c2 current processing time of a query for each model (mean, q1, q2, q3, stddev)
 c4 query results (also written to result.txt)
