@@ -51,8 +51,10 @@ def _positions(shape, seed, n=4096):
 def mutant_missing_product(c, ref):
     """One output without its largest-|x w| product (>= 4 fp16 ulps there, picked so)."""
     k, s, p = c.w.shape[2], c.stride, c.pad
+    cg = c.w.shape[1]                                          # input channels of one group (all of them at groups = 1)
     for b, n, oh, ow in _positions(ref.shape, 1):
-        patch = F.pad(c.x[b], (p, p, p, p))[:, oh * s:oh * s + k, ow * s:ow * s + k]
+        c0 = n // (c.w.shape[0] // c.groups) * cg
+        patch = F.pad(c.x[b, c0:c0 + cg], (p, p, p, p))[:, oh * s:oh * s + k, ow * s:ow * s + k]
         prods = (patch * c.w[n]).flatten()
         d = -prods[prods.abs().argmax()].item()
         if _moves_f16(ref[b, n, oh, ow].item(), d):
@@ -104,11 +106,11 @@ def _rejected(y, expect, ref, within_one_ulp):
 def test_case_qualifies(cid):
     c = CASES[cid]()
     plain, full = c.ref(False, False), c.ref(False, True)      # pre-ReLU; headroom < 1 asserted inside
-    _, q, headroom = X.exact_conv(c.x, c.w, c.bias, c.stride, c.pad, False, c.res, wino=c.wino)
+    _, q, headroom = X.exact_conv(c.x, c.w, c.bias, c.stride, c.pad, False, c.res, wino=c.wino, groups=c.groups)
     assert headroom < 1
 
     # fp32 arithmetic is exact on this data, whatever the order: torch's own conv, and Winograd
-    y32 = F.conv2d(c.x.float(), c.w.float(), c.bias.float(), c.stride, c.pad)
+    y32 = F.conv2d(c.x.float(), c.w.float(), c.bias.float(), c.stride, c.pad, groups=c.groups)
     assert torch.equal(y32.double(), plain)
     if c.wino:
         from idunno.models.packed import wino_weight

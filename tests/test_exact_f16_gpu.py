@@ -12,6 +12,7 @@ import torch
 import exact_ref as X
 import test_band as TB
 import test_c64_f16 as TC
+import test_grouped_gpu as TG
 import test_kernels_gpu as TK
 
 DEV = "cuda"
@@ -30,6 +31,7 @@ STEM_CASES = [(7, 2, 3, 37), (11, 4, 2, 37)]                                    
 LINEAR_CASES = [(5, 512, 1000), (7, 9216, 4096), (130, 2048, 1000)]              # (M, K, N): M 130 leaves a partial tile
 LINEAR_SPLITS = [None, 1, 2, 4, 8]
 SLICE_CASES = [(2, 14, 256, 256, 3, 1, 1), (2, 14, 1024, 256, 1, 1, 0)]
+GROUPED_CASES = TG.CASES                                                         # (B, H, W, C, groups, stride)
 
 
 def tile_case(tile, H):
@@ -81,6 +83,8 @@ def cpu_cases():
         cs[f"stem{(k, s, p, H)}"] = lambda a=(2, H, H, 3, 64, k, s, p): X.conv_case(*a)
     for c in LINEAR_CASES:
         cs[f"linear{c}"] = lambda a=c: X.linear_case(*a)
+    for c in GROUPED_CASES:
+        cs[f"grouped{c}"] = lambda a=c: X.grouped_case(*a)
     return sorted(cs.items())
 
 
@@ -275,3 +279,15 @@ def test_linear_exact(ops, M, K, N, splits):
     for f32 in (False, True):
         _variants(c, lambda relu, r: ops.linear(x, w, b, relu=relu, out_f32=f32, splits=splits).view(M, 1, 1, N),
                   res=(False,), f32=f32)
+
+
+@pytest.mark.parametrize("case", GROUPED_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_conv3x3_grouped_exact(ops, case):
+    """conv3x3_grouped.hip on fp16 operands (block-local weights of pack_grouped_weight):
+    the float64 grouped conv rounded once."""
+    from idunno.models.packed import pack_grouped_weight
+
+    B, H, W, C, groups, stride = case
+    c = X.grouped_case(B, H, W, C, groups, stride)
+    x, w, b = _h(c.x), pack_grouped_weight(c.w.float(), groups).to(DEV), _b(c.bias)
+    _variants(c, lambda relu, r: ops.conv3x3_grouped(x, w, b, groups, stride, relu), res=(False,))
