@@ -54,6 +54,12 @@ def headers() -> list[Path]:
     return sorted(CSRC.rglob("*.h"))
 
 
+# Kernels whose f32 arithmetic is held to a plain fmaf / add chain are compiled without the packed
+# two-float VALU forms (v_pk_add/mul/fma_f32): one f32 operation per instruction, as written.
+SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+SCALAR_F32_SOURCES = {"conv3x3_grouped_f32.hip"}
+
+
 def _compile_cmd(src: Path, obj: Path, incs, abi) -> list[str]:
     cmd = [
         _hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
@@ -63,6 +69,7 @@ def _compile_cmd(src: Path, obj: Path, incs, abi) -> list[str]:
         f"-I{sysconfig.get_paths()['include']}", f"-I{CSRC}",
     ]
     cmd += [f"-I{i}" for i in incs]
+    cmd += SCALAR_F32 if src.name in SCALAR_F32_SOURCES else []
     cmd += ["-c", str(src), "-o", str(obj)]
     return cmd
 

@@ -1,4 +1,4 @@
-// grouped 3x3 conv (ResNeXt bottleneck middle conv): the fp16 and the split-fp16 form.
+// grouped 3x3 conv (ResNeXt bottleneck middle conv): the fp16, the split-fp16 and the fp32 (f32-MFMA) form.
 #include "binding_util.h"
 #include "grouped_math.h"
 
@@ -10,11 +10,15 @@ static const half_t* hp(const torch::Tensor& t) { return reinterpret_cast<const 
 //   x : [B, H, W, C] half, or split [B, H, W, 2C]          C % 32 == 0, Cg = C / groups in {4, 8, 16, 32, 64}
 //   w : [C, 9 CB] half (models/packed.py pack_grouped_weight), split: [C, 2 * 9 CB] (pack_grouped_split_weight)
 //   y : [B, Ho, Wo, C] half, split: [B, Ho, Wo, 2C] (range-guarded)
+// f32: x, w and y are float instead, w [C, 9 CB] (pack_grouped_f32_weight); no acc_scale, no range guard
+enum class GroupedForm { F16, Split, F32 };
+
 static torch::Tensor grouped_impl(torch::Tensor x, torch::Tensor w, torch::Tensor bias, int64_t groups, int64_t stride,
-                                  bool relu, bool split, double acc_scale) {
+                                  bool relu, GroupedForm form, double acc_scale) {
+  const bool split = form == GroupedForm::Split, f32 = form == GroupedForm::F32;
   const auto dev = x.device();
-  check_operand(x, "x", torch::kHalf, 4, dev);
-  check_operand(w, "w", torch::kHalf, 2, dev);
+  check_operand(x, "x", f32 ? torch::kFloat : torch::kHalf, 4, dev);
+  check_operand(w, "w", f32 ? torch::kFloat : torch::kHalf, 2, dev);
   check_operand(bias, "bias", torch::kFloat, 1, dev);
   const int64_t B = x.size(0), H = x.size(1), W = x.size(2), width = split ? 2 : 1, C = x.size(3) / width;
   TORCH_CHECK(C > 0 && x.size(3) == width * C && C % 32 == 0, "x: ", split ? "split input needs 2C halfs with " : "",
@@ -34,6 +38,14 @@ static torch::Tensor grouped_impl(torch::Tensor x, torch::Tensor w, torch::Tenso
               "x: tensor too large for int32 indexing");
   auto y = torch::empty({B, Ho, Wo, width * C}, x.options());
   if (B * Ho * Wo == 0) return y;
+  if (f32) {
+    TORCH_CHECK(conv3x3_grouped_f32_launch(x.data_ptr<float>(), w.data_ptr<float>(), bias.data_ptr<float>(),
+                                           y.data_ptr<float>(), (int)B, (int)H, (int)W, (int)C, (int)groups,
+                                           (int)stride, relu ? 1 : 0, cur_stream()),
+                "conv3x3_grouped_f32: unsupported shape or too many tiles");
+    check_launch("conv3x3_grouped_f32");
+    return y;
+  }
   TORCH_CHECK(conv3x3_grouped_launch(hp(x), hp(w), bias.data_ptr<float>(), reinterpret_cast<half_t*>(y.data_ptr()),
                                      (int)B, (int)H, (int)W, (int)C, (int)groups, (int)stride, relu ? 1 : 0, split,
                                      (float)acc_scale, split ? split_guard_for(dev) : nullptr, cur_stream()),
@@ -44,12 +56,17 @@ static torch::Tensor grouped_impl(torch::Tensor x, torch::Tensor w, torch::Tenso
 
 torch::Tensor conv3x3_grouped(torch::Tensor x, torch::Tensor w, torch::Tensor bias, int64_t groups, int64_t stride,
                               bool relu) {
-  return grouped_impl(x, w, bias, groups, stride, relu, false, 1.0);
+  return grouped_impl(x, w, bias, groups, stride, relu, GroupedForm::F16, 1.0);
 }
 
 torch::Tensor conv3x3_grouped_split(torch::Tensor x, torch::Tensor w, torch::Tensor bias, double acc_scale,
                                     int64_t groups, int64_t stride, bool relu) {
-  return grouped_impl(x, w, bias, groups, stride, relu, true, acc_scale);
+  return grouped_impl(x, w, bias, groups, stride, relu, GroupedForm::Split, acc_scale);
+}
+
+torch::Tensor conv3x3_grouped_f32(torch::Tensor x, torch::Tensor w, torch::Tensor bias, int64_t groups, int64_t stride,
+                                  bool relu) {
+  return grouped_impl(x, w, bias, groups, stride, relu, GroupedForm::F32, 1.0);
 }
 
 bool conv3x3_grouped_ok(int64_t C, int64_t groups, int64_t stride) {

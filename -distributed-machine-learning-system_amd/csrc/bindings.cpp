@@ -44,6 +44,7 @@ Tensor maxpool2d_split(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor ou
 Tensor conv3x3_grouped(Tensor x, Tensor w, Tensor bias, int64_t groups, int64_t stride, bool relu);
 Tensor conv3x3_grouped_split(Tensor x, Tensor w, Tensor bias, double acc_scale, int64_t groups, int64_t stride,
                              bool relu);
+Tensor conv3x3_grouped_f32(Tensor x, Tensor w, Tensor bias, int64_t groups, int64_t stride, bool relu);
 bool conv3x3_grouped_ok(int64_t C, int64_t groups, int64_t stride);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
@@ -167,6 +168,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_grouped_split", &conv3x3_grouped_split,
         "grouped 3x3 pad-1 conv + bias (+relu) on split-fp16 operands (fp32-accurate, range-guarded)", py::arg("x"),
         py::arg("w"), py::arg("bias"), py::arg("acc_scale"), py::arg("groups"), py::arg("stride"), py::arg("relu"));
+  m.def("conv3x3_grouped_f32", &conv3x3_grouped_f32,
+        "grouped 3x3 pad-1 conv + bias (+relu), fp32 NHWC on the f32-input MFMA (exact products, no range guard)",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("groups"), py::arg("stride"), py::arg("relu"));
   m.def("conv3x3_grouped_ok", &conv3x3_grouped_ok, "whether the grouped 3x3 kernel takes (C, groups, stride)");
   m.def("pick_tile_split", &pick_tile_split, "split conv tile heuristic for (M, Cout)");
   m.def("conv2d_nhwc_f32", &conv2d_nhwc_f32, "fp32 implicit-GEMM conv on f32 MFMA + bias (+res) (+relu)",

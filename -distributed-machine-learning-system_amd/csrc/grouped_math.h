@@ -73,5 +73,18 @@ __host__ __device__ __forceinline__ int chan_off(bool split, int c) {
 
 __host__ __device__ constexpr int out_size(int n, int stride) { return (n + 2 - 3) / stride + 1; }
 
+// ---- fp32 form (kernels/conv3x3_grouped_f32.hip) -----------------------------------
+// A staged pixel is its 64 slab channels as 16 chunks of 4 floats, no padding.  Chunk q
+// of the pixel in staged column c is stored at chunk q ^ f32_swz(c, stride): the 16
+// lanes of a ds_read_b128 group read columns col * stride + kx, whose c / stride are 16
+// consecutive values, so they land on 16 different chunks = all 64 banks.
+constexpr int kF32Pixel = kSlab;          // floats from one staged pixel to the next
+constexpr int kF32Chunks = kSlab / 4;     // 16-byte chunks of a staged pixel
+__host__ __device__ constexpr int f32_swz(int c, int stride) { return (c / stride) & (kF32Chunks - 1); }
+// float offset of chunk q of staged pixel `pix`, which lies in staged column c
+__host__ __device__ constexpr int f32_lds_off(int pix, int c, int q, int stride) {
+  return pix * kF32Pixel + ((q ^ f32_swz(c, stride)) << 2);
+}
+
 }  // namespace grouped
 }  // namespace idunno

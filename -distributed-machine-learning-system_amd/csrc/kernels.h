@@ -210,6 +210,10 @@ int conv_glds_pick(int M, int Cout);
 bool conv3x3_grouped_supported(int C, int groups, int stride);
 bool conv3x3_grouped_launch(const half_t* x, const half_t* w, const float* bias, half_t* y, int B, int H, int W, int C,
                             int groups, int stride, int relu, bool split, float acc_scale, int* ovf, hipStream_t st);
+// the same conv on the f32-input MFMA (conv3x3_grouped_f32.hip): x / y NHWC fp32, w fp32 [C][9 CB], exact f32
+// products and f32 accumulation, no range guard.  Same support rule, same false.
+bool conv3x3_grouped_f32_launch(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int C,
+                                int groups, int stride, int relu, hipStream_t st);
 // split-fp16 (fp32-accurate) fused stem, exact-u8 form: w = [2][64][7*32] hi/lo of
 // w * s_c (pre-scaled by 1/acc_scale), bias = folded bias + full sum of w * c_c,
 // psum = [8][8][64] 2D prefix sums of w * c_c over (kh, kw); y = split [B][Hp][Wp][128]

@@ -439,6 +439,13 @@ def pack_grouped_weight(w: torch.Tensor, groups: int, dtype: str = "fp16") -> to
     return _grouped_rows(w.float(), groups).half().contiguous()
 
 
+def pack_grouped_f32_weight(w: torch.Tensor, groups: int) -> torch.Tensor:
+    """[Cout, Cg, 3, 3] -> block-local fp32 weights [Cout, 9 * CB] for
+    ops.conv3x3_grouped_f32: pack_grouped_weight's rows without the rounding to
+    half."""
+    return _grouped_rows(w.float(), groups).contiguous()
+
+
 def pack_grouped_split_weight(w: torch.Tensor, groups: int) -> tuple[torch.Tensor, float]:
     """[Cout, Cg, 3, 3] -> (split block-local weights [Cout, 2 * 9 * CB] half,
     acc_scale): each row is [hi 9 CB | lo 9 CB] of pack_grouped_weight's row,

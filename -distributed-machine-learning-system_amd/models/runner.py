@@ -9,8 +9,8 @@ from dataclasses import dataclass
 
 import torch
 
-from .packed import (Program, expand_grouped_weight, pack_conv_weight, pack_split_tail_weight, pack_split_weight,
-                     program_flops, unpack_grouped_weight, unpack_split_weight)
+from .packed import (Program, expand_grouped_weight, pack_conv_weight, pack_grouped_f32_weight, pack_split_tail_weight,
+                     pack_split_weight, program_flops, unpack_grouped_weight, unpack_split_weight)
 
 _CAPTURE_LOCK = threading.Lock()
 
@@ -87,7 +87,7 @@ class HipRunner:
     GRAPH_SWITCHES = ("split", "split_front", "split_streams", "winograd", "wino_variant", "pack3", "pack3_f16",
                       "side_down", "stem_parts", "front_split", "fuse_stem", "batch_parts", "fuse_down",
                       "fuse_down_1x1", "fuse_next_1x1", "stem_u8", "route", "fuse_down_tail", "astem_form",
-                      "grouped_dense")
+                      "grouped_dense", "grouped_f32")
 
     def __init__(self, program: Program, device=None, fuse_stem: bool = True, front_split: int | None = None,
                  winograd: bool = True, wino_variant: int | None = None, pack3: bool = True):
@@ -173,6 +173,11 @@ class HipRunner:
         # kernel: the A/B baseline and an independent cross-check (tools/ab_flag.py --attr grouped_dense)
         self.grouped_dense = False
         self._gdense: dict = {}
+        # fp32 activations (the all-f32-MFMA path, the range-guard rerun): grouped 3x3 convs on the
+        # grouped f32-MFMA kernel (ops.conv3x3_grouped_f32) instead of the dense fp32 expansion.
+        # Off: the expansion, as before the kernel existed.  ``grouped_dense`` still wins.
+        self.grouped_f32 = False
+        self._gf32: dict = {}
         self.device = torch.device(device or "cuda")
         self.p = program.to(self.device)
         self._graphs: dict[int, tuple] = {}
@@ -421,10 +426,17 @@ class HipRunner:
     def _conv_grouped(self, c, x):
         """A grouped 3x3 conv on fp16 or fp32 activations.  fp16: the grouped
         kernel, or with ``grouped_dense`` the dense conv on the expansion.  fp32
-        (the all-f32-MFMA path and the range-guard rerun, which have no grouped
-        kernel): always the dense fp32 expansion on the direct f32 kernel -- groups x
-        the weight bytes and MFMA work (see ``_grouped_dense``)."""
+        (the all-f32-MFMA path and the range-guard rerun): with ``grouped_f32``
+        and not ``grouped_dense`` the grouped f32-MFMA kernel on block-local fp32
+        rows (built per conv on first use, cached on the runner); else the dense
+        fp32 expansion on the direct f32 kernel -- groups x the weight bytes and
+        MFMA work (see ``_grouped_dense``)."""
         if x.dtype == torch.float32:
+            if self.grouped_f32 and not self.grouped_dense:
+                if id(c) not in self._gf32:
+                    w = unpack_grouped_weight(c) if c.w.dim() != 4 else c.w
+                    self._gf32[id(c)] = pack_grouped_f32_weight(w.cpu(), c.groups).to(self.device)
+                return self.ops.conv3x3_grouped_f32(x, self._gf32[id(c)], c.b, c.groups, c.stride, c.relu)
             return self.ops.conv2d(x, self._grouped_dense(c, "f32"), c.b, 3, 3, c.stride, 1, c.relu)
         if self.grouped_dense:
             return self.ops.conv2d(x, self._grouped_dense(c, "f16"), c.b, 3, 3, c.stride, 1, c.relu,

@@ -13,7 +13,7 @@ __all__ = [
     "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "softmax_topk", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
-    "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_ok",
+    "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -84,6 +84,15 @@ def conv3x3_grouped_split(x, w, bias, acc_scale: float, groups: int, stride: int
     weights (models.packed.pack_grouped_split_weight: [C, 2 * 9 * CB],
     ``acc_scale``): hi*hi + hi*lo + lo*hi in f32; split output, range-guarded."""
     return load().conv3x3_grouped_split(x, w, bias, float(acc_scale), int(groups), int(stride), bool(relu))
+
+
+def conv3x3_grouped_f32(x, w, bias, groups: int, stride: int, relu: bool):
+    """The same conv on NHWC fp32 [B, H, W, C] and fp32 weights
+    (models.packed.pack_grouped_f32_weight: [C, 9 * CB]) on the f32-input MFMA
+    (conv3x3_grouped_f32.hip): exact f32 products, f32 accumulation, fp32 output,
+    no range guard.  ``conv3x3_grouped_ok`` answers the shape question for all
+    three forms."""
+    return load().conv3x3_grouped_f32(x, w, bias, int(groups), int(stride), bool(relu))
 
 
 def conv3x3_grouped_ok(c: int, groups: int, stride: int) -> bool:

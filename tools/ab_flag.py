@@ -7,6 +7,7 @@ device (cdna_hip_programming §5.4 rule 24).
 
 usage: python tools/ab_flag.py --attr side_down [--model resnet18] [--batch 400] [--dtype fp32]
        python tools/ab_flag.py --attr astem_form --values 0,1 --model alexnet --batch 500
+       python tools/ab_flag.py --attr grouped_f32 --set split=0 --model resnext50_32x4d --batch 256
 """
 import argparse
 import os
@@ -27,6 +28,8 @@ def main():
     ap.add_argument("--batch", type=int, default=400)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--set", action="append", default=[], metavar="ATTR=INT",
+                    help="hold another attribute in both arms, e.g. --set split=0 (the all-f32-MFMA path)")
     a = ap.parse_args()
     from idunno import ops
     from idunno.models import HipRunner, build_program
@@ -40,6 +43,10 @@ def main():
     for flag in vals:
         r = HipRunner(prog, dev)
         assert hasattr(r, a.attr), f"HipRunner has no attribute {a.attr!r}"
+        for held in a.set:
+            name, value = held.split("=")
+            assert hasattr(r, name), f"HipRunner has no attribute {name!r}"
+            setattr(r, name, int(value))
         setattr(r, a.attr, flag)
         keep.append(r)
         _start, run = r.capture_window(shard, a.batch)
