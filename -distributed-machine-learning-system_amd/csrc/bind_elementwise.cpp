@@ -1,5 +1,11 @@
-// Memory-bound ops and small utilities: pools, softmax_top1 / softmax_topk, synth_images, graph_launch, tile pickers.
+// Memory-bound ops and small utilities: pools, softmax_top1 / softmax_topk, synth_images, graph_launch, tile pickers,
+// resize_crop_u8.
+#include <map>
+#include <mutex>
+#include <tuple>
+
 #include "binding_util.h"
+#include "resize_math.h"
 
 using namespace idunno;
 
@@ -120,4 +126,78 @@ int64_t pick_tile(int64_t M, int64_t Cout) { return conv_glds_pick((int)M, (int)
 int64_t pick_tile_split(int64_t M, int64_t Cout) { return conv_glds_split_pick((int)M, (int)Cout); }
 int64_t pick_tile_f32(int64_t M, int64_t Cout, int64_t K, bool small) {
   return conv_f32_pick((int)M, (int)Cout, (int)K, small);
+}
+
+// ---- resize_crop_u8 (kernels/resize_u8.hip) ------------------------------------------
+std::tuple<int64_t, int64_t, int64_t, int64_t> resize_crop_geometry_py(int64_t Hi, int64_t Wi, int64_t resize,
+                                                                       int64_t crop);   // bind_stem.cpp
+
+// One geometry's plan and its fixed-point tables on the host (resize_math.h make_plan)
+static resize::Plan resize_u8_host_plan(int64_t Hi, int64_t Wi, int64_t resize, int64_t crop, torch::Tensor& tab) {
+  TORCH_CHECK(Hi >= 1 && Wi >= 1 && Hi <= resize::kMaxDim && Wi <= resize::kMaxDim,
+              "resize_crop_u8: image sides must be in [1, ", resize::kMaxDim, "], got ", Hi, " x ", Wi);
+  TORCH_CHECK(crop >= 1 && crop <= resize::kMaxCrop, "resize_crop_u8: crop must be in [1, ", resize::kMaxCrop, "]");
+  TORCH_CHECK(resize >= crop && resize <= resize::kMaxDim, "resize_crop_u8: resize must be in [crop, ",
+              resize::kMaxDim, "]");
+  const auto [Hr, Wr, top, left] = resize_crop_geometry_py(Hi, Wi, resize, crop);
+  const int ksh = resize::ksize_of((int)Wi, (int)Wr), ksv = resize::ksize_of((int)Hi, (int)Hr);
+  tab = torch::empty({resize::table_ints((int)crop, ksh, ksv)}, torch::TensorOptions().dtype(torch::kInt));
+  std::vector<double> w((size_t)std::max(ksh, ksv));
+  const resize::Plan p = resize::make_plan((int)Hi, (int)Wi, (int)Hr, (int)Wr, (int)top, (int)left, (int)crop,
+                                           tab.data_ptr<int>(), w.data());
+  TORCH_CHECK(p.band >= 1 && p.strip_rows >= 1 && p.lds_bytes <= resize::kLdsBudget,
+              "resize_crop_u8: no plan fits the LDS budget");
+  TORCH_CHECK(!p.chunked || (3 * p.crop + 15) / 16 <= resize::kThreads, "resize_crop_u8: row too wide");
+  return p;
+}
+
+// The plan and the device table of a geometry, built once per (device, Hi, Wi, resize, crop).
+// Entries are never evicted (a table's memory must outlive launches on any stream); past
+// kMaxCached geometries a call builds its own table and hands it to the allocator stream-ordered.
+static std::pair<resize::Plan, torch::Tensor> resize_u8_tables(const torch::Device& dev, int64_t Hi, int64_t Wi,
+                                                               int64_t resize, int64_t crop) {
+  using Key = std::tuple<int, int64_t, int64_t, int64_t, int64_t>;
+  constexpr size_t kMaxCached = 1024;
+  static std::mutex mu;
+  static auto* cache = new std::map<Key, std::pair<resize::Plan, torch::Tensor>>();
+  const Key key{dev.index(), Hi, Wi, resize, crop};
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache->find(key);
+  if (it != cache->end()) return it->second;
+  torch::Tensor host;
+  const resize::Plan p = resize_u8_host_plan(Hi, Wi, resize, crop, host);
+  std::pair<resize::Plan, torch::Tensor> got{p, host.to(dev)};
+  if (cache->size() < kMaxCached) cache->emplace(key, got);
+  else got.second.record_stream(at::hip::getCurrentHIPStream());
+  return got;
+}
+
+torch::Tensor resize_crop_u8(torch::Tensor img, int64_t resize, int64_t crop, c10::optional<torch::Tensor> out) {
+  check_operand(img, "img", torch::kUInt8, 4, img.device());
+  TORCH_CHECK(img.size(3) == 3, "img must be [B, H, W, 3] uint8");
+  const int64_t B = img.size(0), Hi = img.size(1), Wi = img.size(2);
+  TORCH_CHECK(crop >= 1 && crop <= resize::kMaxCrop, "resize_crop_u8: crop must be in [1, ", resize::kMaxCrop, "]");
+  TORCH_CHECK(resize >= crop, "resize_crop_u8: crop larger than resize");
+  auto y = optional_out(out, img.device(), torch::kUInt8, {B, crop, crop, 3});
+  if (!B) return y;
+  const auto [p, tab] = resize_u8_tables(img.device(), Hi, Wi, resize, crop);
+  TORCH_CHECK(B * p.nbands < (int64_t(1) << 31), "resize_crop_u8: batch too large");
+  resize_crop_u8_launch(img.data_ptr<uint8_t>(), y.data_ptr<uint8_t>(), tab.data_ptr<int>(), p, (int)B, cur_stream());
+  check_launch("resize_crop_u8");
+  return y;
+}
+
+// Host only: the plan's fields and the four tables as CPU int32 tensors
+py::dict resize_u8_plan(int64_t Hi, int64_t Wi, int64_t resize, int64_t crop) {
+  torch::Tensor tab;
+  const resize::Plan p = resize_u8_host_plan(Hi, Wi, resize, crop, tab);
+  py::dict d;
+  d["ksh"] = p.ksh; d["ksv"] = p.ksv; d["xlo"] = p.xlo; d["xn"] = p.xn;
+  d["band"] = p.band; d["nbands"] = p.nbands; d["raw_rows"] = p.raw_rows; d["strip_rows"] = p.strip_rows;
+  d["chunked"] = (bool)p.chunked; d["tab_lds"] = (bool)p.tab_lds; d["lds_bytes"] = p.lds_bytes;
+  d["bh"] = tab.slice(0, 0, 2 * crop).view({crop, 2});
+  d["kh"] = tab.slice(0, 2 * crop, p.off_bv).view({crop, p.ksh});
+  d["bv"] = tab.slice(0, p.off_bv, p.off_kv).view({crop, 2});
+  d["kv"] = tab.slice(0, p.off_kv, p.tab_ints).view({crop, p.ksv});
+  return d;
 }

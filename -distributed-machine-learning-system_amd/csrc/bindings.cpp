@@ -78,6 +78,8 @@ Tensor resize_crop(Tensor img, int64_t resize, int64_t crop);
 // bind_elementwise.cpp
 Tensor maxpool2d_nhwc(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out);
 Tensor global_avgpool_nhwc(Tensor x);
+Tensor resize_crop_u8(Tensor img, int64_t resize, int64_t crop, OptTensor out);
+py::dict resize_u8_plan(int64_t Hi, int64_t Wi, int64_t resize, int64_t crop);
 std::vector<Tensor> softmax_top1(Tensor logits, OptTensor packed, OptTensor ovf);
 std::vector<Tensor> softmax_topk(Tensor logits, int64_t k, OptTensor ovf);
 void graph_launch(int64_t exec);
@@ -199,6 +201,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resize_crop_geometry", &resize_crop_geometry_py,
         "host only: (Hr, Wr, top, left) of resize_crop on an Hi x Wi image", py::arg("Hi"), py::arg("Wi"),
         py::arg("resize"), py::arg("crop"));
+  m.def("resize_crop_u8", &resize_crop_u8,
+        "uint8 [B,Hi,Wi,3] -> uint8 [B,crop,crop,3]: Pillow's 8-bit BILINEAR resize of the shorter side + centre crop",
+        py::arg("img"), py::arg("resize"), py::arg("crop"), py::arg("out") = py::none());
+  m.def("resize_u8_plan", &resize_u8_plan,
+        "host only: resize_crop_u8's launch plan and fixed-point tables (bh, kh, bv, kv) for one geometry",
+        py::arg("Hi"), py::arg("Wi"), py::arg("resize"), py::arg("crop"));
   m.def("maxpool2d_nhwc", &maxpool2d_nhwc, "NHWC max pool (into ``out`` when given)", py::arg("x"), py::arg("k"),
         py::arg("s"), py::arg("pad"), py::arg("out") = py::none());
   m.def("global_avgpool_nhwc", &global_avgpool_nhwc, "NHWC global average pool");

@@ -242,6 +242,13 @@ void preprocess_launch(const uint8_t* img, half_t* out, long npix, const long lo
                        long long start_off, long long max_start, long long sub, long pix_per_img, hipStream_t st);
 void resize_crop_launch(const uint8_t* img, half_t* out, int B, int Hi, int Wi, int Hr, int Wr,
                         int crop, int top, int left, hipStream_t st);
+// uint8 [B, Hi, Wi, 3] -> uint8 [B, crop, crop, 3] in Pillow's 8-bit BILINEAR arithmetic (resize_u8.hip);
+// `tab` and `p` are one geometry's device table and plan (resize_math.h make_plan)
+namespace resize {
+struct Plan;
+}
+void resize_crop_u8_launch(const uint8_t* img, uint8_t* out, const int* tab, const resize::Plan& p, int B,
+                           hipStream_t st);
 void maxpool_launch(const half_t* x, half_t* y, int B, int H, int W, int C, int Ho, int Wo, int k,
                     int s, int pad, hipStream_t st);
 void avgpool_launch(const half_t* x, half_t* y, int B, int HW, int C, hipStream_t st);

@@ -76,9 +76,14 @@ class HipRunner:
     """Runs a packed Program through the gfx950 kernels.
 
     ``forward(img_u8)`` takes uint8 [B,224,224,3] on the GPU and returns
-    (class int32 [B], prob fp32 [B]).  ``capture(batch)`` records the whole
+    (class int32 [B], prob fp32 [B]).  A batch of any other size [B,H,W,3] is
+    resized (shorter side to 256) and centre-cropped to 224 first: fp32
+    programs, and fp16 ones with ``resize_u8``, through ``ops.resize_crop_u8``
+    (Pillow's filter on uint8, then the fused uint8 stems); fp16 programs
+    by default through ``ops.resize_crop``.  ``capture(batch)`` records the whole
     forward into a hipGraph (torch.cuda.CUDAGraph == hipGraph on ROCm) with a
-    static input buffer, removing per-kernel launch overhead.
+    static [batch,224,224,3] input buffer, removing per-kernel launch overhead;
+    batches of other sizes are eager.
     """
 
     # the kernel-choice switches a captured graph depends on: ``_variant()`` reads
@@ -87,7 +92,7 @@ class HipRunner:
     GRAPH_SWITCHES = ("split", "split_front", "split_streams", "winograd", "wino_variant", "pack3", "pack3_f16",
                       "side_down", "stem_parts", "front_split", "fuse_stem", "batch_parts", "fuse_down",
                       "fuse_down_1x1", "fuse_next_1x1", "stem_u8", "route", "fuse_down_tail", "astem_form",
-                      "grouped_dense", "grouped_f32")
+                      "grouped_dense", "grouped_f32", "resize_u8")
 
     def __init__(self, program: Program, device=None, fuse_stem: bool = True, front_split: int | None = None,
                  winograd: bool = True, wino_variant: int | None = None, pack3: bool = True):
@@ -178,6 +183,12 @@ class HipRunner:
         # Off: the expansion, as before the kernel existed.  ``grouped_dense`` still wins.
         self.grouped_f32 = False
         self._gf32: dict = {}
+        # fp16 programs on batches that are not 224x224: True = ops.resize_crop_u8 (Pillow's
+        # antialiasing BILINEAR on uint8, the JPEG source's pixels) and then the fused uint8 stems;
+        # False = ops.resize_crop (2x2 bilinear, normalised fp16 out) and the unfused stem conv + max
+        # pool, as before the uint8 kernel existed.  fp32 programs always take the uint8 kernel:
+        # they refused such batches before.  (A/B: tools/ab_flag.py --attr resize_u8)
+        self.resize_u8 = False
         self.device = torch.device(device or "cuda")
         self.p = program.to(self.device)
         self._graphs: dict[int, tuple] = {}
@@ -244,6 +255,10 @@ class HipRunner:
         native = tuple(img_u8.shape[1:3]) == (224, 224)
         if ims.start is not None and not native:
             raise ValueError("device-side windows need 224x224 shards")
+        if not native and (p.dtype == "fp32" or self.resize_u8):
+            # any other size: Pillow's resize + centre crop on uint8 (ops.resize_crop_u8, the JPEG
+            # source's pixels), then exactly the path a 224x224 batch takes, fused uint8 stems included
+            return self._logits(_Images(o.resize_crop_u8(img_u8, 256, 224)))
         parts = self.batch_parts or 1
         if p.kind == "resnet" and native and parts > 1 and ims.n >= 2 * parts:
             return self._logits_in_parts(ims, parts)
@@ -314,8 +329,7 @@ class HipRunner:
         """Reference-precision forward: every activation, weight and product in
         fp32 (conv_f32.hip on the f32-input MFMA, elementwise_f32.hip)."""
         o, p = self.ops, self.p
-        if not native:
-            raise ValueError("the fp32 path takes 224x224 inputs (resize on host first)")
+        assert native, "_logits resizes other sizes first"
         first = p.stem if p.kind == "resnet" else p.features[0][1]
         nb = ims.n
         if p.kind == "resnet" and self.split and self._split_ok():

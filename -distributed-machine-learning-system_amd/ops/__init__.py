@@ -10,7 +10,7 @@ from __future__ import annotations
 from ._ext import available, load, so_path
 
 __all__ = [
-    "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_geometry",
+    "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_u8", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "softmax_topk", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
@@ -312,6 +312,16 @@ def preprocess(img_u8, start=None, batch: int = -1, start_offset: int = 0, windo
 def resize_crop(img_u8, resize: int = 256, crop: int = 224):
     """Resize(shorter side) + CenterCrop + normalise, fused."""
     return load().resize_crop(img_u8, resize, crop)
+
+
+def resize_crop_u8(img_u8, resize: int = 256, crop: int = 224, out=None):
+    """uint8 [B,Hi,Wi,3] -> uint8 [B,crop,crop,3] (into ``out`` when given): the shorter
+    side resized to ``resize`` with Pillow's ``Image.resize(..., BILINEAR)`` -- its
+    support-scaled triangle filter in its 8-bit fixed-point arithmetic, so the bytes are
+    Pillow's -- and the centre crop of ``resize_crop_geometry``.  What ``GpuJpegSource``
+    does to a decoded JPEG, for batches that arrive decoded; the output is the
+    224x224x3 form the fused uint8 stems take.  ``crop`` <= 256, sides <= 16384."""
+    return load().resize_crop_u8(img_u8, int(resize), int(crop), out)
 
 
 def resize_crop_geometry(hi: int, wi: int, resize: int = 256, crop: int = 224):

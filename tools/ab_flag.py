@@ -8,6 +8,7 @@ device (cdna_hip_programming §5.4 rule 24).
 usage: python tools/ab_flag.py --attr side_down [--model resnet18] [--batch 400] [--dtype fp32]
        python tools/ab_flag.py --attr astem_form --values 0,1 --model alexnet --batch 500
        python tools/ab_flag.py --attr grouped_f32 --set split=0 --model resnext50_32x4d --batch 256
+       python tools/ab_flag.py --attr resize_u8 --dtype fp16 --hw 300,400     (eager: graphs take 224x224 only)
 """
 import argparse
 import os
@@ -30,6 +31,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--set", action="append", default=[], metavar="ATTR=INT",
                     help="hold another attribute in both arms, e.g. --set split=0 (the all-f32-MFMA path)")
+    ap.add_argument("--hw", default=None, metavar="H,W",
+                    help="time the eager forward on a seeded uint8 noise batch of this size instead of the "
+                         "captured graph on 224x224 (the runner resizes other sizes itself)")
     a = ap.parse_args()
     from idunno import ops
     from idunno.models import HipRunner, build_program
@@ -38,6 +42,10 @@ def main():
     dev = torch.device("cuda")
     prog = build_program(a.model, dtype=a.dtype)
     shard = ops.synth_images(1234, 0, a.batch, dev)
+    if a.hw:
+        h, w = (int(v) for v in a.hw.split(","))
+        gen = torch.Generator(device=dev).manual_seed(1234)
+        shard = torch.randint(0, 256, (a.batch, h, w, 3), dtype=torch.uint8, device=dev, generator=gen)
     runs, outs, keep = {}, {}, []
     vals = (False, True) if not a.values else tuple(int(v) for v in a.values.split(","))
     for flag in vals:
@@ -49,7 +57,10 @@ def main():
             setattr(r, name, int(value))
         setattr(r, a.attr, flag)
         keep.append(r)
-        _start, run = r.capture_window(shard, a.batch)
+        if a.hw:
+            run = lambda r=r: r.forward(shard)
+        else:
+            _start, run = r.capture_window(shard, a.batch)
         runs[flag] = run
         cls, prob = run()
         torch.cuda.synchronize()
