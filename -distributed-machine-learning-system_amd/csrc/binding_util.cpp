@@ -3,6 +3,8 @@
 
 #include <mutex>
 
+#include "float_input_math.h"
+
 namespace idunno {
 
 const int kRouteNoBand = 1, kRouteNoC64 = 2, kRouteNoStream1x1 = 4, kRouteLegacySmallM = 8, kRouteC64TwoPerCU = 16,
@@ -115,17 +117,10 @@ void check_strided_input(const torch::Tensor& x2, int B, int Ho, int Wo, int64_t
               "x2 must be the block input at `stride` of x1's resolution");
 }
 
-// Packed-row geometry of an RGB stem (conv_f32 mode 2 / conv_glds pack3,
-// preprocess_pack3): nc row copies (the distinct 16-byte phases of 3*stride*ox
-// for E = 16 / elem_bytes elements per chunk), wp elements each, cpk 16-byte
-// chunks per kernel row.
+// Packed-row geometry of an RGB stem: float_input_math.h pack3_geometry_of, the one definition
+// the producers (preprocess_pack3*, float_to_pack3*) and the consumers (conv2d_pack3*) share.
 void pack3_geometry(int W, int KW, int stride, int pad, int elem_bytes, int& nc, int& wp, int& cpk) {
-  const int E = 16 / elem_bytes;
-  int g = 1;                                   // gcd(3 * stride, E), E a power of two
-  while (g < E && (3 * stride) % (2 * g) == 0) g *= 2;
-  nc = E / g;
-  wp = (3 * (W + 2 * pad) + E - 1 + E - 1) / E * E;
-  cpk = (3 * KW + E - 1) / E;
+  pack3_geometry_of(W, KW, stride, pad, elem_bytes, nc, wp, cpk);
 }
 
 const long long* window_args(const torch::Tensor& img, const c10::optional<torch::Tensor>& start, int64_t batch,

@@ -75,6 +75,10 @@ Tensor preprocess_pack3_split(Tensor img, int64_t KW, int64_t stride, int64_t pa
 std::tuple<int64_t, int64_t, int64_t, int64_t> resize_crop_geometry_py(int64_t Hi, int64_t Wi, int64_t resize,
                                                                        int64_t crop);
 Tensor resize_crop(Tensor img, int64_t resize, int64_t crop);
+// bind_float_input.cpp
+Tensor float_to_nhwc4(Tensor x, bool f32);
+Tensor float_to_pack3(Tensor x, int64_t KW, int64_t stride, int64_t pad, bool f16);
+Tensor float_to_pack3_split(Tensor x, int64_t KW, int64_t stride, int64_t pad);
 // bind_elementwise.cpp
 Tensor maxpool2d_nhwc(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out);
 Tensor global_avgpool_nhwc(Tensor x);
@@ -197,6 +201,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_fused", &stem_fused, "fused normalise + conv7x7/2 + bias + relu + maxpool3x3/2 (ResNet stem)",
         py::arg("img"), py::arg("w"), py::arg("bias"), py::arg("start") = py::none(), py::arg("batch") = -1,
         py::arg("start_offset") = 0, py::arg("window") = -1, py::arg("sub") = 0);
+  m.def("float_to_nhwc4", &float_to_nhwc4, "normalised float [B,3,H,W] (NCHW or channels-last) -> fp16 (or fp32) NHWC4",
+        py::arg("x"), py::arg("f32") = false);
+  m.def("float_to_pack3", &float_to_pack3, "normalised float [B,3,H,W] -> packed-row fp32 (or fp16) stem input",
+        py::arg("x"), py::arg("KW"), py::arg("stride"), py::arg("pad"), py::arg("f16") = false);
+  m.def("float_to_pack3_split", &float_to_pack3_split,
+        "normalised float [B,3,H,W] -> split-fp16 packed-row stem input (range-guarded)", py::arg("x"), py::arg("KW"),
+        py::arg("stride"), py::arg("pad"));
   m.def("resize_crop", &resize_crop, "bilinear resize + centre crop + normalise");
   m.def("resize_crop_geometry", &resize_crop_geometry_py,
         "host only: (Hr, Wr, top, left) of resize_crop on an Hi x Wi image", py::arg("Hi"), py::arg("Wi"),

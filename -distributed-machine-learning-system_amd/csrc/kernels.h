@@ -127,6 +127,26 @@ void preprocess_pack3_split_launch(const uint8_t* img, half_t* out, int B, int H
 void preprocess_f32_launch(const uint8_t* img, float* out, long npix, const long long* start_idx,
                            long long start_off, long long max_start, long long sub, long pix_per_img,
                            hipStream_t st);
+// Normalised float image (fp32 / fp16, logical [B,3,H,W], NCHW or channels-last strides) -> a
+// stem operand (float_input.hip).  No arithmetic but the fp16 rounding / the hi-lo split.
+enum FloatInForm {
+  kFiNhwc4F16 = 0,   // [B][H][W][4] fp16, 4th channel 0   (what preprocess writes)
+  kFiNhwc4F32,       // the same in fp32                   (preprocess, f32)
+  kFiPack3F32,       // [B][H][nc][wp] fp32                (preprocess_pack3)
+  kFiPack3F16,       // [B][H][nc][wp] fp16                (preprocess_pack3, f16)
+  kFiPack3Split,     // [B][H][2][nc][wp] fp16 hi, lo      (preprocess_pack3_split)
+};
+struct FloatInArgs {
+  const void* src;
+  void* out;
+  long long sb;        // source strides in elements: image, ...
+  long long sc, sh;    // ... channel plane (NCHW; unused for channels-last) and row
+  int B, H, W;
+  int rows, nbands;    // float_input_math.h fi_band_rows(W) and the bands per image
+  int pad, nc, wp;     // packed rows: left zero pixels, row copies, elements per copy row
+  int* guard;          // split form: the range-guard flag, or null
+};
+void float_input_launch(const FloatInArgs& a, bool src_f16, bool channels_last, FloatInForm form, hipStream_t st);
 void maxpool_f32_launch(const float* x, float* y, int B, int H, int W, int C, int Ho, int Wo, int k, int s,
                         int pad, hipStream_t st);
 void avgpool_f32_launch(const float* x, float* y, int B, int HW, int C, hipStream_t st);

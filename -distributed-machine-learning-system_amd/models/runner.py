@@ -54,6 +54,15 @@ class _Images:
         return self.batch if self.start is not None else self.img.shape[0]
 
     @property
+    def is_float(self) -> bool:
+        """A normalised float batch [B,3,H,W] (NCHW or channels-last) instead of uint8 [B,H,W,3]."""
+        return self.img.dtype != torch.uint8
+
+    @property
+    def hw(self) -> tuple:
+        return tuple(self.img.shape[2:4] if self.is_float else self.img.shape[1:3])
+
+    @property
     def where(self) -> tuple:
         """The ops' trailing ``start, batch, start_offset, window, sub`` arguments."""
         return self.start, self.batch, self.start_offset, self.window, self.sub
@@ -84,6 +93,14 @@ class HipRunner:
     forward into a hipGraph (torch.cuda.CUDAGraph == hipGraph on ROCm) with a
     static [batch,224,224,3] input buffer, removing per-kernel launch overhead;
     batches of other sizes are eager.
+
+    In place of the uint8 batch ``forward`` / ``logits`` also take images that
+    are already normalised: float32 or float16 of logical shape [B,3,224,224],
+    contiguous (NCHW), ``torch.channels_last`` or a batch view of either, read
+    in place by ``ops.float_to_*`` (float_input.hip).  Nothing is normalised or
+    resampled; a float batch takes the unfused stem (producer -> stem conv ->
+    max pool) of its precision, never the fused uint8 stems.
+    ``capture(batch, in_dtype=torch.float32)`` is the graph of that input.
     """
 
     # the kernel-choice switches a captured graph depends on: ``_variant()`` reads
@@ -225,6 +242,8 @@ class HipRunner:
         forward that tripped it is recomputed on the all-f32 kernels (one host
         read of the flag per eager call)."""
         ims = _Images(img_u8, start, batch, start_offset)
+        if ims.is_float:
+            self._check_float(img_u8, start)
         if not self._guarded():
             return self._logits(ims)
         self._ovf.zero_()
@@ -240,6 +259,18 @@ class HipRunner:
             self._ovf.zero_()
         return out
 
+    @staticmethod
+    def _check_float(x, start) -> None:
+        """A non-uint8 batch must be a normalised float batch the float-input kernels take."""
+        if x.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"images must be uint8 [B,H,W,3] or float32/float16 [B,3,224,224], got {x.dtype}")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"float images must have logical shape [B,3,224,224], got {tuple(x.shape)}")
+        if tuple(x.shape[2:]) != (224, 224):
+            raise ValueError(f"float images are not resampled: 224x224 only, got {tuple(x.shape[2:])}")
+        if start is not None:
+            raise ValueError("device-side windows (start=) read uint8 shards, not float batches")
+
     def logits_f32_exact(self, img_u8, start=None, batch: int = -1, start_offset: int = 0):
         """The same forward on the all-f32-MFMA kernels (fp32 range)."""
         self.overflow_reruns += 1
@@ -252,7 +283,7 @@ class HipRunner:
 
     def _logits(self, ims: _Images) -> torch.Tensor:
         o, p, img_u8 = self.ops, self.p, ims.img
-        native = tuple(img_u8.shape[1:3]) == (224, 224)
+        native = ims.hw == (224, 224)
         if ims.start is not None and not native:
             raise ValueError("device-side windows need 224x224 shards")
         if not native and (p.dtype == "fp32" or self.resize_u8):
@@ -266,11 +297,11 @@ class HipRunner:
             return self._logits_f32(ims, native)
         s = p.stem
         fused = (self.fuse_stem and native and p.kind == "resnet" and s.small and s.kh == 7 and s.kw == 7
-                 and s.stride == 2 and s.pad == 3 and s.cout == 64)
+                 and s.stride == 2 and s.pad == 3 and s.cout == 64 and not ims.is_float)
         first = p.features[0][1] if p.kind != "resnet" else None
         feats = p.features
         # AlexNet: uint8 -> conv1 + ReLU + max pool in one phased MFMA kernel (alex_stem.hip)
-        if first is not None and native and self._alex_stem_fusable(first, feats[1:]):
+        if first is not None and native and not ims.is_float and self._alex_stem_fusable(first, feats[1:]):
             x = o.alex_stem_u8_f16(img_u8, first.fs, first.fs_bias, first.fs_psum, first.fs_scale, *ims.where,
                                    form=self.astem_form)
             feats = feats[2:]
@@ -279,12 +310,12 @@ class HipRunner:
             # vs 704 for NHWC4 on the register-staged conv_igemm): conv 290 -> 220
             # us at B=500, but the packed-row preprocess costs 133 vs 46 us, so it
             # is off by default (profiles/r2_v21_alexnet_f16_pack3.md)
-            x3 = o.preprocess_pack3(img_u8, first.kw, first.stride, first.pad, *ims.where, f16=True)
-            x = o.conv2d_pack3(x3, first.p3, first.b, img_u8.shape[2], first.kh, first.kw, first.stride, first.pad,
+            x3 = self._pack3(ims, first, f16=True)
+            x = o.conv2d_pack3(x3, first.p3, first.b, ims.hw[1], first.kh, first.kw, first.stride, first.pad,
                                first.relu)
             feats = feats[1:]
         elif not fused:
-            x = o.preprocess(img_u8, *ims.where) if native else o.resize_crop(img_u8, 256, 224)
+            x = self._nhwc4(ims) if native else o.resize_crop(img_u8, 256, 224)
         if p.kind == "resnet":
             split = self.front_split if self.front_split is not None else \
                 (2 if p.name in ("resnet18", "resnet34") and ims.n >= 256 else 1)
@@ -336,7 +367,7 @@ class HipRunner:
             # fused split stem (uint8 -> normalise -> conv7x7/2 -> ReLU -> max
             # pool, split out; or stem conv + max pool into the split layout)
             # -> split residual stages (the last conv writes fp32) -> fp32 avgpool / FC
-            fused = self.fuse_stem and first.fs is not None and first.relu
+            fused = self.fuse_stem and first.fs is not None and first.relu and not ims.is_float
             if fused and (self.split_streams or 1) > 1 and nb >= 64 and ims.img.is_cuda:
                 return self._split_dual_stream(ims)
             parts = self.split_front or 1
@@ -406,19 +437,33 @@ class HipRunner:
 
     def _stem_f32(self, first, ims: _Images):
         """fp32 RGB stem conv (+ReLU) of a window / part of the images."""
-        o, img_u8 = self.ops, ims.img
+        o, width = self.ops, ims.hw[1]
         if self.split and first.sp3 is not None:
             # split-fp16 packed rows (fp32-accurate) on the f16 MFMA, fp32 output
-            x3 = o.preprocess_pack3_split(img_u8, first.kw, first.stride, first.pad, *ims.where)
-            return o.conv2d_pack3_split(x3, first.sp3, first.b, first.s_scale, img_u8.shape[2], first.kh, first.kw,
+            if ims.is_float:
+                x3 = o.float_to_pack3_split(ims.img, first.kw, first.stride, first.pad)
+            else:
+                x3 = o.preprocess_pack3_split(ims.img, first.kw, first.stride, first.pad, *ims.where)
+            return o.conv2d_pack3_split(x3, first.sp3, first.b, first.s_scale, width, first.kh, first.kw,
                                         first.stride, first.pad, first.relu)
         if self.pack3 and first.p3 is not None:
             # packed rows: K 176 vs 224 for the 7x7/2, 400 vs 528 for the 11x11/4
-            x3 = o.preprocess_pack3(img_u8, first.kw, first.stride, first.pad, *ims.where)
-            return o.conv2d_pack3(x3, first.p3, first.b, img_u8.shape[2], first.kh, first.kw, first.stride,
+            return o.conv2d_pack3(self._pack3(ims, first), first.p3, first.b, width, first.kh, first.kw, first.stride,
                                   first.pad, first.relu)
-        x = o.preprocess(img_u8, *ims.where, f32=True)
+        x = self._nhwc4(ims, f32=True)
         return o.conv2d(x, first.w, first.b, first.kh, first.kw, first.stride, first.pad, first.relu)
+
+    def _nhwc4(self, ims: _Images, f32: bool = False):
+        """The NHWC4 stem operand: normalised from uint8, or laid out from a float batch."""
+        if ims.is_float:
+            return self.ops.float_to_nhwc4(ims.img, f32)
+        return self.ops.preprocess(ims.img, *ims.where, f32=f32)
+
+    def _pack3(self, ims: _Images, first, f16: bool = False):
+        """The packed-row operand of the stem conv ``first``, from either kind of input."""
+        if ims.is_float:
+            return self.ops.float_to_pack3(ims.img, first.kw, first.stride, first.pad, f16)
+        return self.ops.preprocess_pack3(ims.img, first.kw, first.stride, first.pad, *ims.where, f16=f16)
 
     def _grouped_dense(self, c, kind: str):
         """The dense block-diagonal expansion of a grouped conv (``groups`` x its
@@ -587,7 +632,7 @@ class HipRunner:
         FCs (split-K), fp32 logits."""
         o, p = self.ops, self.p
         feats = p.features[1:]
-        if self._alex_stem_fusable(first, feats):
+        if not ims.is_float and self._alex_stem_fusable(first, feats):
             x = o.alex_stem_split(ims.img, first.fs, first.fs_bias, first.fs_psum, first.fs_scale, *ims.where,
                                   form=self.astem_form)
             feats = feats[1:]
@@ -796,7 +841,11 @@ class HipRunner:
         return tuple(int(self.fuse_down_tail) if n == "fuse_down_tail" else getattr(self, n)
                      for n in self.GRAPH_SWITCHES)
 
-    def _capture_key(self, batch: int, packed=None, slot: int = 0, topk: int | None = None):
+    def _capture_key(self, batch: int, packed=None, slot: int = 0, topk: int | None = None, in_dtype=None):
+        if in_dtype not in (None, torch.uint8):     # float-input graphs; the uint8 keys stay as they were
+            if in_dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"in_dtype must be torch.uint8, float32 or float16, got {in_dtype}")
+            return (("in", str(in_dtype)), self._capture_key(batch, packed, slot, topk))
         if topk is not None:        # its own graphs; topk=None keeps the key it always had
             return (("topk", int(topk), batch, slot), self._variant())
         return ((batch if slot == 0 else (batch, slot)) if packed is None else ("pk", batch, packed.data_ptr()),
@@ -806,9 +855,9 @@ class HipRunner:
         return ("win", shard.data_ptr(), tuple(shard.shape), batch, None if start is None else start.data_ptr(),
                 start_offset, None if packed is None else packed.data_ptr(), self._variant())
 
-    def has_graph(self, batch: int, packed=None, slot: int = 0, topk: int | None = None) -> bool:
-        """Whether ``capture(batch, packed=, slot=, topk=)`` would replay an existing graph."""
-        return self._capture_key(batch, packed, slot, self._check_topk(topk, packed)) in self._graphs
+    def has_graph(self, batch: int, packed=None, slot: int = 0, topk: int | None = None, in_dtype=None) -> bool:
+        """Whether ``capture(batch, packed=, slot=, topk=, in_dtype=)`` would replay an existing graph."""
+        return self._capture_key(batch, packed, slot, self._check_topk(topk, packed), in_dtype) in self._graphs
 
     def has_window(self, shard: torch.Tensor, batch: int, packed: torch.Tensor | None = None) -> bool:
         """A window graph over ``shard`` (own start scalar) is already captured."""
@@ -851,17 +900,23 @@ class HipRunner:
         self._graphs[key] = (g, keep, sout)
 
     def capture(self, batch: int, hw: int = 224, packed: torch.Tensor | None = None, slot: int = 0,
-                topk: int | None = None):
+                topk: int | None = None, in_dtype=None):
         """Capture forward for a fixed batch; returns (static_in, replay_fn).
         With ``packed`` the graph also writes (class, prob bits) pairs into
         that caller-owned buffer (e.g. a collective round's send buffer).
         ``slot`` > 0 captures an independent copy (own static buffers), so two
         forwards of the same batch size can be in flight.  An integer ``topk``
-        captures its own graph, whose replay returns [batch, topk] tensors."""
+        captures its own graph, whose replay returns [batch, topk] tensors.
+        ``in_dtype`` = torch.float32 / float16 captures the graph of a normalised
+        float batch instead: its static input is [batch,3,224,224] (NCHW) of that
+        dtype, and it coexists with the uint8 graph of the same batch size."""
         topk = self._check_topk(topk, packed)
-        key = self._capture_key(batch, packed, slot, topk)
+        key = self._capture_key(batch, packed, slot, topk, in_dtype)
         if key not in self._graphs:
-            sin = torch.zeros(batch, hw, hw, 3, dtype=torch.uint8, device=self.device)
+            if in_dtype in (None, torch.uint8):
+                sin = torch.zeros(batch, hw, hw, 3, dtype=torch.uint8, device=self.device)
+            else:
+                sin = torch.zeros(batch, 3, hw, hw, dtype=in_dtype, device=self.device)
             self._capture_graph(key, lambda: self.forward(sin, packed=packed, topk=topk), sin)
         g, sin, sout = self._graphs[key]
         return sin, self._replayer(g, sout, packed)

@@ -13,6 +13,7 @@ __all__ = [
     "available", "load", "so_path", "conv2d", "linear", "preprocess", "resize_crop", "resize_crop_u8", "resize_crop_geometry",
     "maxpool2d", "global_avgpool", "softmax_top1", "softmax_topk", "pick_tile", "pick_tile_f32", "synth_images", "stem_fused",
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
+    "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
@@ -232,6 +233,27 @@ def preprocess_pack3(img_u8, kw: int, stride: int, pad: int, start=None, batch: 
     """uint8 [B,H,W,3] -> packed-row stem input [B, H, nc, wp], fp32 (``f16``:
     fp16) (window args as ``preprocess``)."""
     return load().preprocess_pack3(img_u8, kw, stride, pad, start, batch, start_offset, window, sub, f16)
+
+
+def float_to_nhwc4(x, f32: bool = False):
+    """Normalised float [B,3,H,W] (fp32 / fp16; NCHW, channels-last or a batch
+    view of either, read in place) -> NHWC4 fp16 [B,H,W,4] (``f32``: fp32), 4th
+    channel 0: ``preprocess``'s output for input that is already normalised
+    (float_input.hip).  Values are copied (fp16: rounded to nearest even)."""
+    return load().float_to_nhwc4(x, f32)
+
+
+def float_to_pack3(x, kw: int, stride: int, pad: int, f16: bool = False):
+    """The same input -> packed-row stem input [B, H, nc, wp] fp32 (``f16``:
+    fp16), ``preprocess_pack3``'s output."""
+    return load().float_to_pack3(x, kw, stride, pad, f16)
+
+
+def float_to_pack3_split(x, kw: int, stride: int, pad: int):
+    """The same input -> split-fp16 packed rows [B, H, 2*nc, wp],
+    ``preprocess_pack3_split``'s output; sets the armed split guard on a value
+    that is not finite or has |v| >= 65504."""
+    return load().float_to_pack3_split(x, kw, stride, pad)
 
 
 def conv2d_pack3(x3, w, bias, width: int, kh: int, kw: int, stride: int, pad: int, relu: bool, tile: int = -1):
