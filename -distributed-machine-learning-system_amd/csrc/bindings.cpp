@@ -46,6 +46,9 @@ Tensor conv3x3_grouped_split(Tensor x, Tensor w, Tensor bias, double acc_scale, 
                              bool relu);
 Tensor conv3x3_grouped_f32(Tensor x, Tensor w, Tensor bias, int64_t groups, int64_t stride, bool relu);
 bool conv3x3_grouped_ok(int64_t C, int64_t groups, int64_t stride);
+// bind_conv_dw.cpp, bind_conv1x1_narrow.cpp
+Tensor conv3x3_dw(Tensor x, Tensor w9, Tensor bias, int64_t stride, int64_t act, bool clamp_in, OptTensor out);
+Tensor conv1x1_narrow(Tensor x, Tensor w, Tensor bias, int64_t act, OptTensor residual, OptTensor out);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -178,6 +181,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped 3x3 pad-1 conv + bias (+relu), fp32 NHWC on the f32-input MFMA (exact products, no range guard)",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("groups"), py::arg("stride"), py::arg("relu"));
   m.def("conv3x3_grouped_ok", &conv3x3_grouped_ok, "whether the grouped 3x3 kernel takes (C, groups, stride)");
+  m.def("conv3x3_dw", &conv3x3_dw,
+        "depthwise 3x3 pad-1 conv + bias (+ReLU / ReLU6), fp16 or fp32 NHWC; clamp_in: min(x, 6) on the input",
+        py::arg("x"), py::arg("w9"), py::arg("bias"), py::arg("stride"), py::arg("act"), py::arg("clamp_in") = false,
+        py::arg("out") = py::none());
+  m.def("conv1x1_narrow", &conv1x1_narrow,
+        "1x1 conv over channel counts that are multiples of 8 + bias (+residual) (+ReLU / ReLU6), fp16 or fp32 NHWC",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("residual") = py::none(),
+        py::arg("out") = py::none());
+  m.def("conv1x1_narrow_kpad", [](int64_t K, bool f32) { return (int64_t)conv1x1_narrow_kpad((int)K, f32); },
+        "row length of conv1x1_narrow's weights for K input channels", py::arg("K"), py::arg("f32"));
   m.def("pick_tile_split", &pick_tile_split, "split conv tile heuristic for (M, Cout)");
   m.def("conv2d_nhwc_f32", &conv2d_nhwc_f32, "fp32 implicit-GEMM conv on f32 MFMA + bias (+res) (+relu)",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("res"), py::arg("KH"), py::arg("KW"), py::arg("stride"),

@@ -287,6 +287,17 @@ void softmax_top1_launch(const float* logits, int ld, int N, int rows, int* cls,
 void softmax_topk_launch(const float* logits, int ld, int N, int rows, int k, int* cls, float* prob,
                          const int* ovf, hipStream_t st);
 
+// ---- depthwise-separable convs (MobileNetV2): conv3x3_dw.hip, conv1x1_narrow.hip ----
+// y = act(conv3x3 depthwise(min(x, 6) if clamp_in else x; stride 1 | 2, pad 1) + bias); x, w [9, C], y fp16, or
+// fp32 with f32; C % 8 == 0 (fp32: % 4); act 0 none, 1 ReLU, 2 ReLU6.  False: unsupported shape, nothing launched.
+bool conv3x3_dw_launch(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C,
+                       int stride, int act, int clamp_in, bool f32, hipStream_t st);
+// y[M, N] = act(x[M, K] w[N, Kp]^T + bias (+ res[M, N])): x rows ldx elements apart, w zero from K to
+// Kp = conv1x1_narrow_kpad(K, f32); K, N multiples of 8, <= 1280.  False: unsupported shape, nothing launched.
+bool conv1x1_narrow_launch(const void* x, int ldx, const void* w, const float* bias, const void* res, void* y, int M,
+                           int K, int N, int act, bool f32, hipStream_t st);
+int conv1x1_narrow_kpad(int K, bool f32);
+
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.

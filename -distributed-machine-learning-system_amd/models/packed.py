@@ -14,6 +14,9 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
     transform U = G g G^T [16, Cout, Cin] (conv_wino_f32.hip)
   * grouped 3x3 convs (ResNeXt) -> channel-block-local [Cout, 9 * CB] weights
     (pack_grouped_weight / pack_grouped_split_weight), never a dense expansion
+  * depthwise 3x3 convs (MobileNetV2) -> tap-major [9, C] weights (pack_dw_weight),
+    its 1x1 convs -> [Cout, Kp] rows zero-padded to the narrow kernel's K step
+    (pack_pw_weight); both in the program's precision, true fp32 for dtype "fp32"
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -60,6 +63,13 @@ class Conv:
     # programs and the plain fp32 [Cout, Cin/groups, 3, 3] weight in fp32 programs, whose ``sw`` is
     # the block-local split form (pack_grouped_split_weight); cin / cout stay the full widths
     groups: int = 1
+    act: int | None = None   # epilogue: 0 none, 1 ReLU, 2 ReLU6; None = from ``relu``
+    dw: bool = False         # depthwise 3x3: ``w`` is tap-major [9, C] (pack_dw_weight), groups = C
+    narrow: bool = False     # 1x1 on the narrow-channel kernel: ``w`` is [Cout, Kp] (pack_pw_weight)
+
+    def __post_init__(self):
+        if self.act is None:
+            self.act = 1 if self.relu else 0
 
     def to(self, device):
         vals = {f.name: getattr(self, f.name) for f in fields(self)}
@@ -81,12 +91,32 @@ class Block:
 
 
 @dataclass
+class MBlock:
+    """MobileNetV2 inverted residual: expand 1x1 (None at t = 1), depthwise 3x3,
+    project 1x1 (no activation); ``residual``: + the block's input."""
+    expand: Conv | None
+    dw: Conv
+    project: Conv
+    residual: bool
+
+    def to(self, device):
+        return replace(self, expand=self.expand.to(device) if self.expand else None, dw=self.dw.to(device),
+                       project=self.project.to(device))
+
+    @property
+    def convs(self):
+        return [c for c in (self.expand, self.dw, self.project) if c is not None]
+
+
+@dataclass
 class Program:
     name: str
-    kind: str                 # "resnet" | "alexnet"
+    kind: str                 # "resnet" | "alexnet" | "mobilenet"
     stem: Conv | None = None  # resnet
     blocks: list = field(default_factory=list)
     features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p))
+    mblocks: list = field(default_factory=list)   # mobilenet: list[MBlock] between ``stem`` and ``last``
+    last: Conv | None = None                      # mobilenet: the 1x1 before the pool
     fcs: list = field(default_factory=list)       # list[Conv] as 1x1 convs (last -> fp32 logits)
     num_classes: int = 1000
     dtype: str = "fp16"       # activation / weight precision: "fp16" | "fp32" (reference precision)
@@ -95,6 +125,7 @@ class Program:
         return replace(self, stem=self.stem.to(device) if self.stem else None,
                        blocks=[b.to(device) for b in self.blocks],
                        features=[(k, v.to(device) if k == "conv" else v) for k, v in self.features],
+                       mblocks=[b.to(device) for b in self.mblocks], last=self.last.to(device) if self.last else None,
                        fcs=[f.to(device) for f in self.fcs])
 
     def param_bytes(self) -> int:
@@ -113,6 +144,10 @@ class Program:
         for k, v in self.features:
             if k == "conv":
                 yield v
+        for mb in self.mblocks:
+            yield from mb.convs
+        if self.last is not None:
+            yield self.last
         yield from self.fcs
 
 
@@ -198,6 +233,10 @@ def pack3_eligible(cin: int, kw: int, stride: int = 2, dtype: str = "fp32") -> b
 def unpack_conv_weight(c: Conv) -> torch.Tensor:
     """Inverse of pack_conv_weight -> fp32 [Cout, Cin, KH, KW] (a grouped conv:
     [Cout, Cin / groups, 3, 3], its fp32 copy in fp32 programs)."""
+    if c.dw:
+        return unpack_dw_weight(c.w)
+    if c.narrow:
+        return unpack_pw_weight(c.w, c.cin)
     if c.groups > 1:
         return c.w.float().contiguous() if c.w.dim() == 4 else unpack_grouped_weight(c)
     w = c.w.float()
@@ -483,6 +522,70 @@ def expand_grouped_weight(w: torch.Tensor, groups: int) -> torch.Tensor:
     return dense
 
 
+# ---------------------------------------------------------------------------
+# depthwise-separable convs (MobileNetV2): conv3x3_dw.hip, conv1x1_narrow.hip
+# ---------------------------------------------------------------------------
+
+def _dt(dtype: str) -> torch.dtype:
+    if dtype not in DTYPES:
+        raise ValueError(f"dtype must be one of {DTYPES}, got {dtype!r}")
+    return torch.float32 if dtype == "fp32" else torch.float16
+
+
+def pack_dw_weight(w: torch.Tensor, dtype: str = "fp16") -> torch.Tensor:
+    """Depthwise [C, 1, 3, 3] -> tap-major [9, C] (tap = 3 kh + kw) in the
+    program's precision: a lane's 8 (fp16) / 4 (fp32) channels of one tap are
+    one 16-byte load."""
+    if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
+        raise ValueError(f"depthwise weights must be [C, 1, 3, 3], got {tuple(w.shape)}")
+    return w.float().reshape(w.shape[0], 9).t().to(_dt(dtype)).contiguous()
+
+
+def unpack_dw_weight(w9: torch.Tensor) -> torch.Tensor:
+    """Inverse of pack_dw_weight -> fp32 [C, 1, 3, 3]."""
+    return w9.float().t().reshape(w9.shape[1], 1, 3, 3).contiguous()
+
+
+def pw_kpad(k: int, dtype: str = "fp16") -> int:
+    """Row length of conv1x1_narrow's weights: K up to the kernel's K step (32 fp16, 16 fp32)."""
+    step = 16 if dtype == "fp32" else 32
+    return -(-k // step) * step
+
+
+def pack_pw_weight(w: torch.Tensor, dtype: str = "fp16") -> torch.Tensor:
+    """Pointwise [N, K, 1, 1] -> [N, Kp] in the program's precision, Kp =
+    pw_kpad(K), zero from K (K = 24 and 144 are no multiples of 32)."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or w.shape[0] % 8 or w.shape[1] % 8:
+        raise ValueError(f"pointwise weights must be [N, K, 1, 1] with N and K multiples of 8, got {tuple(w.shape)}")
+    n, k = w.shape[:2]
+    p = torch.zeros(n, pw_kpad(k, dtype), dtype=_dt(dtype))
+    p[:, :k] = w.float().reshape(n, k).to(p.dtype)
+    return p
+
+
+def unpack_pw_weight(wp: torch.Tensor, k: int) -> torch.Tensor:
+    """Inverse of pack_pw_weight -> fp32 [N, K, 1, 1]."""
+    return wp[:, :k].float().reshape(wp.shape[0], k, 1, 1).contiguous()
+
+
+def make_dw(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int, dtype: str = "fp16") -> Conv:
+    c = conv.in_channels
+    if conv.groups != c or conv.out_channels != c or conv.kernel_size != (3, 3) or conv.padding != (1, 1) \
+            or conv.stride[0] not in (1, 2) or c % 8:
+        raise ValueError(f"depthwise convs are 3x3 pad-1 stride-1/2 with C % 8 == 0, got {conv}")
+    w, b = fold_bn(conv.weight, conv.bias, bn)
+    return Conv(w=pack_dw_weight(w, dtype), b=b.contiguous(), cin=c, cout=c, kh=3, kw=3, stride=conv.stride[0], pad=1,
+                relu=act != 0, groups=c, act=act, dw=True)
+
+
+def make_pw(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int, dtype: str = "fp16") -> Conv:
+    if conv.kernel_size != (1, 1) or conv.stride != (1, 1) or conv.padding != (0, 0) or conv.groups != 1:
+        raise ValueError(f"narrow 1x1 convs are dense, stride 1, pad 0, got {conv}")
+    w, b = fold_bn(conv.weight, conv.bias, bn)
+    return Conv(w=pack_pw_weight(w, dtype), b=b.contiguous(), cin=conv.in_channels, cout=conv.out_channels, kh=1, kw=1,
+                stride=1, pad=0, relu=act != 0, act=act, narrow=True)
+
+
 # Winograd F(2x2, 3x3) filter transform (Lavin & Gray): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
@@ -597,6 +700,19 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
                  make_fc(lins[2], False, dtype=dt)]
         p.num_classes = lins[2].out_features
         return p
+    if isinstance(m, ref.MobileNetV2):
+        f = m.features
+        p = Program(name, "mobilenet", stem=make_conv(f[0][0], f[0][1], True, dt), dtype=dt)
+        p.stem.act = 2          # ReLU6: the small-C kernels stop at ReLU, the first depthwise conv clamps its input
+        for blk in list(f)[1:-1]:
+            mods = list(blk.conv)
+            expand = make_pw(mods[0][0], mods[0][1], 2, dt) if len(mods) == 4 else None
+            p.mblocks.append(MBlock(expand, make_dw(mods[-3][0], mods[-3][1], 2, dt), make_pw(mods[-2], mods[-1], 0, dt),
+                                    blk.use_res))
+        p.last = make_pw(f[-1][0], f[-1][1], 2, dt)
+        p.fcs = [make_fc(m.classifier[1], False, dtype=dt)]
+        p.num_classes = m.classifier[1].out_features
+        return p
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
@@ -621,7 +737,7 @@ def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torc
     y = F.conv2d(x, unpack_conv_weight(c).to(x.device), c.b.to(x.device), c.stride, c.pad, groups=c.groups)
     if res is not None:
         y = y + res
-    return F.relu(y) if c.relu else y
+    return y.clamp(0.0, 6.0) if c.act == 2 else F.relu(y) if c.act else y
 
 
 @torch.no_grad()
@@ -637,6 +753,12 @@ def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
                 y = _emu_conv(c, y)
             x = _emu_conv(blk.convs[-1], y, idt)
         x = x.mean(dim=(2, 3))
+    elif p.kind == "mobilenet":
+        x = _emu_conv(p.stem, x)
+        for mb in p.mblocks:
+            y = x if mb.expand is None else _emu_conv(mb.expand, x)
+            x = _emu_conv(mb.project, _emu_conv(mb.dw, y), x if mb.residual else None)
+        x = _emu_conv(p.last, x).mean(dim=(2, 3))
     else:
         for k, v in p.features:
             x = _emu_conv(v, x) if k == "conv" else F.max_pool2d(x, *v)
@@ -667,6 +789,12 @@ def program_flops(p: Program, hw: int = 224) -> float:
             if blk.down is not None:
                 hd = out_hw(hin, blk.down)
                 tot += hd * hd * blk.down.flops_per_out_pixel
+    elif p.kind == "mobilenet":
+        h = out_hw(hw, p.stem)
+        tot += h * h * p.stem.flops_per_out_pixel
+        for c in [c for mb in p.mblocks for c in mb.convs] + [p.last]:
+            h = out_hw(h, c)
+            tot += h * h * c.flops_per_out_pixel
     else:
         h = hw
         for k, v in p.features:

@@ -133,6 +133,65 @@ class AlexNet(nn.Module):
         return self.classifier(torch.flatten(x, 1))
 
 
+def _conv_bn_relu6(cin, cout, k=3, s=1, groups=1):
+    """torchvision v0.10's ConvBNActivation: [Conv2d(bias=False), BatchNorm2d, ReLU6]."""
+    return nn.Sequential(_conv(cin, cout, k, s, (k - 1) // 2, groups), nn.BatchNorm2d(cout), nn.ReLU6(inplace=True))
+
+
+class InvertedResidual(nn.Module):
+    """MobileNetV2 block: [1x1 expand-BN-ReLU6 (absent at t = 1)], depthwise
+    3x3-BN-ReLU6, 1x1 project, BN; + x where stride 1 and cin == cout, and no
+    activation after the add."""
+
+    def __init__(self, cin, cout, stride, t):
+        super().__init__()
+        hidden = cin * t
+        self.use_res = stride == 1 and cin == cout
+        layers = [_conv_bn_relu6(cin, hidden, 1)] if t != 1 else []
+        layers += [_conv_bn_relu6(hidden, hidden, 3, stride, groups=hidden), _conv(hidden, cout, 1),
+                   nn.BatchNorm2d(cout)]
+        self.conv = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.conv(x) if self.use_res else self.conv(x)
+
+
+MOBILENET_V2_SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2),
+                         (6, 320, 1, 1))       # (t, c, n, s)
+
+
+class MobileNetV2(nn.Module):
+    """torchvision v0.10's mobilenet_v2 at width 1.0 (3,504,872 parameters)."""
+
+    def __init__(self, num_classes=1000):
+        super().__init__()
+        feats, cin = [_conv_bn_relu6(3, 32, 3, 2)], 32
+        for t, c, n, s in MOBILENET_V2_SETTINGS:
+            for i in range(n):
+                feats.append(InvertedResidual(cin, c, s if i == 0 else 1, t))
+                cin = c
+        feats.append(_conv_bn_relu6(cin, 1280, 1))
+        self.features = nn.Sequential(*feats)
+        self.classifier = nn.Sequential(nn.Dropout(0.2), nn.Linear(1280, num_classes))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out")
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, 0, 0.01)
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        x = self.features(x).mean(dim=(2, 3))
+        return self.classifier(x)
+
+
+def mobilenet_v2(num_classes=1000):
+    return MobileNetV2(num_classes)
+
+
 def resnet18(num_classes=1000):
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes)
 
@@ -173,11 +232,11 @@ def alexnet(num_classes=1000):
     return AlexNet(num_classes)
 
 
-# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet
+# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2
 BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet,
             "resnet101": resnet101, "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d,
             "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
-            "wide_resnet101_2": wide_resnet101_2}
+            "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -234,7 +293,8 @@ def build(name: str, seed: int = 0, randomize_bn: bool = False) -> nn.Module:
 ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18",
            "resnet-50": "resnet50", "alex": "alexnet", "resnet-101": "resnet101", "resnet-152": "resnet152",
            "resnext50": "resnext50_32x4d", "resnext101": "resnext101_32x8d",
-           "wide_resnet50": "wide_resnet50_2", "wide_resnet101": "wide_resnet101_2"}
+           "wide_resnet50": "wide_resnet50_2", "wide_resnet101": "wide_resnet101_2",
+           "mobilenet": "mobilenet_v2", "mobilenetv2": "mobilenet_v2", "mobilenet-v2": "mobilenet_v2"}
 
 
 def canonical(name: str) -> str:

@@ -230,7 +230,8 @@ class HipRunner:
 
     # -- eager forward ------------------------------------------------------
     def _guarded(self) -> bool:
-        return self.p.dtype == "fp32" and self.split and self._split_ok()
+        # MobileNetV2 has no split path (its fp32 program is true fp32), hence no range guard
+        return self.p.kind != "mobilenet" and self.p.dtype == "fp32" and self.split and self._split_ok()
 
     def logits(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
                start_offset: int = 0) -> torch.Tensor:
@@ -293,6 +294,8 @@ class HipRunner:
         parts = self.batch_parts or 1
         if p.kind == "resnet" and native and parts > 1 and ims.n >= 2 * parts:
             return self._logits_in_parts(ims, parts)
+        if p.kind == "mobilenet":
+            return self._logits_mobilenet(ims, native)
         if p.dtype == "fp32":
             return self._logits_f32(ims, native)
         s = p.stem
@@ -340,6 +343,26 @@ class HipRunner:
             last = i == len(p.fcs) - 1
             x = o.linear(x, fc.w, fc.b, relu=fc.relu, out_f32=last)
         return x
+
+    def _logits_mobilenet(self, ims: _Images, native):
+        """MobileNetV2 in either precision (fp32: true fp32 on the f32 MFMA): NHWC4
+        producer -> small-C stem conv with ReLU -> per block narrow 1x1 expand
+        (ReLU6), depthwise 3x3 (ReLU6; the first one also finishes the stem's ReLU6
+        by clamping its input), narrow 1x1 project (+ residual) -> 1x1 to 1280
+        (ReLU6) -> average pool -> FC.  Everything on the current stream."""
+        o, p, s = self.ops, self.p, self.p.stem
+        f32 = p.dtype == "fp32"
+        x = self._nhwc4(ims, f32=f32) if native else o.resize_crop(ims.img, 256, 224)
+        x = o.conv2d(x, s.w, s.b, s.kh, s.kw, s.stride, s.pad, True)
+        for i, mb in enumerate(p.mblocks):
+            y = x
+            if mb.expand is not None:
+                y = o.conv1x1_narrow(y, mb.expand.w, mb.expand.b, mb.expand.act)
+            y = o.conv3x3_dw(y, mb.dw.w, mb.dw.b, mb.dw.stride, mb.dw.act, clamp_in=i == 0)
+            x = o.conv1x1_narrow(y, mb.project.w, mb.project.b, mb.project.act, residual=x if mb.residual else None)
+        x = o.conv1x1_narrow(x, p.last.w, p.last.b, p.last.act)
+        x = o.global_avgpool(x)
+        return o.linear(x, p.fcs[0].w, p.fcs[0].b, relu=False, out_f32=True)
 
     def _alex_stem_fusable(self, first, feats) -> bool:
         """conv1 has the fused-stem operands and ``feats`` (what follows it)

@@ -15,6 +15,7 @@ __all__ = [
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
+    "conv3x3_dw", "conv1x1_narrow",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -99,6 +100,25 @@ def conv3x3_grouped_f32(x, w, bias, groups: int, stride: int, relu: bool):
 def conv3x3_grouped_ok(c: int, groups: int, stride: int) -> bool:
     """Whether the grouped 3x3 kernel takes ``c`` channels in ``groups`` groups at ``stride``."""
     return bool(load().conv3x3_grouped_ok(int(c), int(groups), int(stride)))
+
+
+def conv3x3_dw(x, w9, bias, stride: int, act: int, clamp_in: bool = False, out=None):
+    """Depthwise 3x3 pad-1 conv (stride 1 or 2) + bias + activation on NHWC
+    [B, H, W, C], fp16 (C % 8 == 0) or fp32 (C % 4 == 0) by ``x``'s dtype, any H
+    and W (conv3x3_dw.hip; f32 accumulation).  ``w9`` = models.packed.pack_dw_weight
+    ([9, C] tap-major, x's dtype), ``bias`` fp32 [C]; ``act`` 0 none, 1 ReLU, 2
+    ReLU6.  ``clamp_in`` applies min(x, 6) to the input: the ReLU6 of a producer
+    that only has ReLU."""
+    return load().conv3x3_dw(x, w9, bias, int(stride), int(act), bool(clamp_in), out)
+
+
+def conv1x1_narrow(x, w, bias, act: int, residual=None, out=None):
+    """1x1 conv + bias (+ ``residual``, added before the activation) on NHWC
+    [B, H, W, K] with K and N only multiples of 8 (<= 1280), fp16 or true fp32 by
+    ``x``'s dtype (conv1x1_narrow.hip).  ``x`` may be a channel slice of a wider
+    NHWC tensor.  ``w`` = models.packed.pack_pw_weight ([N, Kp], zero from K);
+    ``act`` 0 none, 1 ReLU, 2 ReLU6."""
+    return load().conv1x1_narrow(x, w, bias, int(act), residual, out)
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,
