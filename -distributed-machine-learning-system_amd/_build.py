@@ -58,7 +58,7 @@ def headers() -> list[Path]:
 # two-float VALU forms (v_pk_add/mul/fma_f32): one f32 operation per instruction, as written.
 SCALAR_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SCALAR_F32_SOURCES = {"conv3x3_grouped_f32.hip", "resize_u8.hip", "float_input.hip", "conv3x3_dw.hip",
-                      "conv1x1_narrow.hip"}
+                      "conv1x1_narrow.hip", "conv_dw_kxk.hip", "se_excite.hip"}
 
 
 def _compile_cmd(src: Path, obj: Path, incs, abi) -> list[str]:

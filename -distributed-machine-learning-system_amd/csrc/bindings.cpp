@@ -48,7 +48,11 @@ Tensor conv3x3_grouped_f32(Tensor x, Tensor w, Tensor bias, int64_t groups, int6
 bool conv3x3_grouped_ok(int64_t C, int64_t groups, int64_t stride);
 // bind_conv_dw.cpp, bind_conv1x1_narrow.cpp
 Tensor conv3x3_dw(Tensor x, Tensor w9, Tensor bias, int64_t stride, int64_t act, bool clamp_in, OptTensor out);
-Tensor conv1x1_narrow(Tensor x, Tensor w, Tensor bias, int64_t act, OptTensor residual, OptTensor out);
+Tensor conv1x1_narrow(Tensor x, Tensor w, Tensor bias, int64_t act, OptTensor residual, OptTensor out,
+                      OptTensor in_scale, int64_t res_act);
+Tensor conv_dw(Tensor x, Tensor w, Tensor bias, int64_t k, int64_t stride, int64_t act, int64_t act_in, OptTensor pool,
+               OptTensor out);
+Tensor se_excite(Tensor mean, Tensor w1, Tensor b1, Tensor w2, Tensor b2);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -186,9 +190,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("w9"), py::arg("bias"), py::arg("stride"), py::arg("act"), py::arg("clamp_in") = false,
         py::arg("out") = py::none());
   m.def("conv1x1_narrow", &conv1x1_narrow,
-        "1x1 conv over channel counts that are multiples of 8 + bias (+residual) (+ReLU / ReLU6), fp16 or fp32 NHWC",
+        "1x1 conv over channel counts that are multiples of 8 + bias (+residual) (+activation), fp16 or fp32 NHWC; "
+        "in_scale [B, K]: per-image input scale; res_act 3: hardswish on the residual",
         py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("residual") = py::none(),
-        py::arg("out") = py::none());
+        py::arg("out") = py::none(), py::arg("in_scale") = py::none(), py::arg("res_act") = 0);
+  m.def("conv_dw", &conv_dw,
+        "depthwise k x k conv (k 3 | 5, pad k / 2) + bias (+ReLU / ReLU6 / hardswish), fp16 or fp32 NHWC; act_in 3: "
+        "hardswish on the input; pool [B, C]: also the spatial mean of the output",
+        py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("k"), py::arg("stride"), py::arg("act"),
+        py::arg("act_in") = 0, py::arg("pool") = py::none(), py::arg("out") = py::none());
+  m.def("se_excite", &se_excite, "hardsigmoid(w2 relu(w1 mean + b1) + b2) in one launch, fp16 or fp32",
+        py::arg("mean"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"));
   m.def("conv1x1_narrow_kpad", [](int64_t K, bool f32) { return (int64_t)conv1x1_narrow_kpad((int)K, f32); },
         "row length of conv1x1_narrow's weights for K input channels", py::arg("K"), py::arg("f32"));
   m.def("pick_tile_split", &pick_tile_split, "split conv tile heuristic for (M, Cout)");

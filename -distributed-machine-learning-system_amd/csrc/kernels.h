@@ -294,9 +294,25 @@ bool conv3x3_dw_launch(const void* x, const void* w, const float* bias, void* y,
                        int stride, int act, int clamp_in, bool f32, hipStream_t st);
 // y[M, N] = act(x[M, K] w[N, Kp]^T + bias (+ res[M, N])): x rows ldx elements apart, w zero from K to
 // Kp = conv1x1_narrow_kpad(K, f32); K, N multiples of 8, <= 1280.  False: unsupported shape, nothing launched.
+// act 3 hardswish, 4 hardsigmoid; in_scale [M / hw, K] (x's dtype): every row of x is multiplied by its image's
+// scale row as it is staged, the product rounded to x's dtype; res_act 3: hardswish on res as it is read.
 bool conv1x1_narrow_launch(const void* x, int ldx, const void* w, const float* bias, const void* res, void* y, int M,
-                           int K, int N, int act, bool f32, hipStream_t st);
+                           int K, int N, int act, bool f32, hipStream_t st, const void* in_scale = nullptr, int hw = 1,
+                           int res_act = 0);
 int conv1x1_narrow_kpad(int K, bool f32);
+
+// ---- MobileNetV3: conv_dw_kxk.hip, se_excite.hip ----
+// y = act(depthwise k x k conv(act_in(x); k 3 | 5, stride 1 | 2, pad k / 2) + bias); x, w [k k, C], y fp16, or fp32
+// with f32; C % 8 == 0 (fp32: % 4); act 0 none, 1 ReLU, 2 ReLU6, 3 hardswish; act_in 0 none, 3 hardswish.  pool
+// (x's dtype, [B, C], or null): also the spatial mean of y as stored, without atomics; needs conv_dw_pool_ok(Wo).
+// False: unsupported shape, nothing launched.
+bool conv_dw_kxk_launch(const void* x, const void* w, const float* bias, void* y, void* pool, int B, int H, int W, int C,
+                        int k, int stride, int act, int act_in, bool f32, hipStream_t st);
+bool conv_dw_pool_ok(int Wo);
+// scale[B, C] = hardsigmoid(w2 relu(w1 mean + b1) + b2): mean, scale and the weights (w1 [Csq, kpad(C)],
+// w2 [C, kpad(Csq)], conv1x1_narrow's layout) fp16, or fp32 with f32; C <= 1280, Csq <= 320, multiples of 8.
+bool se_excite_launch(const void* mean, const void* w1, const float* b1, const void* w2, const float* b2, void* scale,
+                      int B, int C, int Csq, bool f32, hipStream_t st);
 
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has

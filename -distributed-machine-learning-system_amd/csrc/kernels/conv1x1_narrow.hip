@@ -35,6 +35,13 @@
 //     trades halves between the pair's fragments (v_permlane16_swap, f16_pair_off) for one
 //     16-byte store a lane.  Rows past M and channel chunks past N are predicated off: N is
 //     a multiple of 8, so an 8-channel chunk is whole or absent, and outputs are not padded.
+//   * MobileNetV3 adds hardswish / hardsigmoid epilogues (act 3 / 4), a hardswish on the
+//     residual as it is read (res_act 3: the residual is a stem output whose hardswish its
+//     consumers finish) and, as the SCALE instantiations, a squeeze-and-excitation input
+//     scale: while a row is staged it is multiplied by its own image's row of
+//     in_scale[B, K] (image = row / hw: a tile spans several images at 7 x 7 and 14 x 14),
+//     the product rounded to the activations' dtype as the module's ``scale * x`` is.  The
+//     scaled tensor never exists in HBM.  The instantiations without SCALE are unchanged.
 #include "../common.h"
 #include "../kernels.h"
 #include "../launch_util.h"
@@ -51,6 +58,9 @@ struct PwArgs {
   int ldx;              // elements between pixels of x
   int act;
   int wm;               // waves over M fragments: 1, 2 or 4 (<= MF)
+  const void* in_scale; // [M / hw, K] in x's dtype (SCALE instantiations)
+  int hw;               // pixels per image
+  int res_act;          // 3: hardswish on the residual as read
 };
 
 constexpr int kPwLdsBytes = 16 * (1280 * 4 + 16);   // one M fragment of the widest fp32 rows: 80.25 KiB
@@ -75,12 +85,16 @@ struct PwFrag<float> {
 };
 
 __device__ __forceinline__ float pw_act(float v, int act) {
+  if (act >= 3) {                                         // 3 hardswish, 4 hardsigmoid
+    const float h = fminf(fmaxf(v + 3.f, 0.f), 6.f) * (1.f / 6.f);
+    return act == 3 ? v * h : h;
+  }
   if (act) v = fmaxf(v, 0.f);
   if (act == 2) v = fminf(v, 6.f);
   return v;
 }
 
-template <typename T, int MF>
+template <typename T, int MF, bool SCALE>
 __global__ void __launch_bounds__(256) conv1x1_narrow_kernel(const PwArgs a) {
   constexpr int E = 16 / (int)sizeof(T);    // elements per 16-byte chunk
   constexpr int KS = 4 * E;                 // K step: four lane groups of one chunk
@@ -111,7 +125,15 @@ __global__ void __launch_bounds__(256) conv1x1_narrow_kernel(const PwArgs a) {
         if (i < total) {
           const int m = i / cpr, c = i - m * cpr;
           off[j] = m * pitch + c * 16;
-          if (m0 + m < a.M && c < kvc) v[j] = *reinterpret_cast<const V*>(xb + (size_t)(m0 + m) * a.ldx + c * E);
+          if (m0 + m < a.M && c < kvc) {
+            v[j] = *reinterpret_cast<const V*>(xb + (size_t)(m0 + m) * a.ldx + c * E);
+            if constexpr (SCALE) {
+              const V s = *reinterpret_cast<const V*>(static_cast<const T*>(a.in_scale) +
+                                                      (size_t)((m0 + m) / a.hw) * a.K + c * E);
+#pragma unroll
+              for (int e = 0; e < E; ++e) v[j][e] = (T)((float)v[j][e] * (float)s[e]);
+            }
+          }
         }
       }
 #pragma unroll
@@ -175,12 +197,12 @@ __global__ void __launch_bounds__(256) conv1x1_narrow_kernel(const PwArgs a) {
           if (n0 < a.N) {
             const half4v r = *reinterpret_cast<const half4v*>(rp + n0);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v0[e] += (float)r[e];
+            for (int e = 0; e < 4; ++e) v0[e] += a.res_act == 3 ? (float)(half_t)pw_act((float)r[e], 3) : (float)r[e];
           }
           if (n1 < a.N) {
             const half4v r = *reinterpret_cast<const half4v*>(rp + n1);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v1[e] += (float)r[e];
+            for (int e = 0; e < 4; ++e) v1[e] += a.res_act == 3 ? (float)(half_t)pw_act((float)r[e], 3) : (float)r[e];
           }
         }
         half4v o0, o1;
@@ -195,8 +217,17 @@ __global__ void __launch_bounds__(256) conv1x1_narrow_kernel(const PwArgs a) {
       } else {
         if (a.res != nullptr && mok) {
           const float* rp = static_cast<const float*>(a.res) + rowoff;
-          if (n0 < a.N) v0 += *reinterpret_cast<const float4v*>(rp + n0);
-          if (n1 < a.N) v1 += *reinterpret_cast<const float4v*>(rp + n1);
+          float4v r0 = n0 < a.N ? *reinterpret_cast<const float4v*>(rp + n0) : zf;
+          float4v r1 = n1 < a.N ? *reinterpret_cast<const float4v*>(rp + n1) : zf;
+          if (a.res_act == 3) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              r0[e] = pw_act(r0[e], 3);
+              r1[e] = pw_act(r1[e], 3);
+            }
+          }
+          v0 += r0;
+          v1 += r1;
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -216,17 +247,24 @@ int conv1x1_narrow_kpad(int K, bool f32) {
   return (K + ks - 1) / ks * ks;
 }
 
+template <typename T, int MF, bool SCALE>
+static void pw_launch_as(const PwArgs& a, int lds, hipStream_t st) {
+  ensure_lds_attr(reinterpret_cast<const void*>(&conv1x1_narrow_kernel<T, MF, SCALE>), kPwLdsBytes);
+  const int grid = (a.M + 16 * MF - 1) / (16 * MF);
+  hipLaunchKernelGGL((conv1x1_narrow_kernel<T, MF, SCALE>), dim3(grid), dim3(256), lds, st, a);
+}
+
 template <typename T, int MF>
 static void pw_launch(const PwArgs& a, int lds, hipStream_t st) {
-  ensure_lds_attr(reinterpret_cast<const void*>(&conv1x1_narrow_kernel<T, MF>), kPwLdsBytes);
-  const int grid = (a.M + 16 * MF - 1) / (16 * MF);
-  hipLaunchKernelGGL((conv1x1_narrow_kernel<T, MF>), dim3(grid), dim3(256), lds, st, a);
+  if (a.in_scale != nullptr) pw_launch_as<T, MF, true>(a, lds, st);
+  else pw_launch_as<T, MF, false>(a, lds, st);
 }
 
 bool conv1x1_narrow_launch(const void* x, int ldx, const void* w, const float* bias, const void* res, void* y, int M,
-                           int K, int N, int act, bool f32, hipStream_t st) {
-  if (M <= 0 || K <= 0 || N <= 0 || K % 8 || N % 8 || K > 1280 || N > 1280 || ldx < K || act < 0 || act > 2)
+                           int K, int N, int act, bool f32, hipStream_t st, const void* in_scale, int hw, int res_act) {
+  if (M <= 0 || K <= 0 || N <= 0 || K % 8 || N % 8 || K > 1280 || N > 1280 || ldx < K || act < 0 || act > 4)
     return false;
+  if ((in_scale != nullptr && (hw <= 0 || M % hw)) || (res_act != 0 && res_act != 3)) return false;
   PwArgs a{};
   a.x = x;
   a.w = w;
@@ -237,6 +275,9 @@ bool conv1x1_narrow_launch(const void* x, int ldx, const void* w, const float* b
   a.Kp = conv1x1_narrow_kpad(K, f32);
   a.ldx = ldx;
   a.act = act;
+  a.in_scale = in_scale;
+  a.hw = hw;
+  a.res_act = res_act;
   const int pitch = a.Kp * (f32 ? 4 : 2) + 16;
   int mf = 4;
   while (mf > 1 && (16 * mf * pitch > kPwLdsBytes || 16 * (mf / 2) >= M)) mf /= 2;   // fits LDS; no all-idle fragments

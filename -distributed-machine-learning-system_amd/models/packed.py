@@ -17,6 +17,8 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
   * depthwise 3x3 convs (MobileNetV2) -> tap-major [9, C] weights (pack_dw_weight),
     its 1x1 convs -> [Cout, Kp] rows zero-padded to the narrow kernel's K step
     (pack_pw_weight); both in the program's precision, true fp32 for dtype "fp32"
+  * MobileNetV3: the same two forms (depthwise 5x5 -> [25, C]); the squeeze-and-
+    excitation FCs and the classifier's first Linear are pointwise weights too
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -63,8 +65,8 @@ class Conv:
     # programs and the plain fp32 [Cout, Cin/groups, 3, 3] weight in fp32 programs, whose ``sw`` is
     # the block-local split form (pack_grouped_split_weight); cin / cout stay the full widths
     groups: int = 1
-    act: int | None = None   # epilogue: 0 none, 1 ReLU, 2 ReLU6; None = from ``relu``
-    dw: bool = False         # depthwise 3x3: ``w`` is tap-major [9, C] (pack_dw_weight), groups = C
+    act: int | None = None   # epilogue: 0 none, 1 ReLU, 2 ReLU6, 3 hardswish, 4 hardsigmoid; None = from ``relu``
+    dw: bool = False         # depthwise k x k: ``w`` is tap-major [k k, C] (pack_dw_weight), groups = C
     narrow: bool = False     # 1x1 on the narrow-channel kernel: ``w`` is [Cout, Kp] (pack_pw_weight)
 
     def __post_init__(self):
@@ -92,16 +94,20 @@ class Block:
 
 @dataclass
 class MBlock:
-    """MobileNetV2 inverted residual: expand 1x1 (None at t = 1), depthwise 3x3,
-    project 1x1 (no activation); ``residual``: + the block's input."""
+    """MobileNetV2 / V3 inverted residual: expand 1x1 (None when it would not
+    widen), depthwise k x k, project 1x1 (no activation); ``residual``: + the
+    block's input.  V3's squeeze-and-excitation: ``se`` = (fc1, fc2) as pointwise
+    convs on the depthwise output's spatial mean (ReLU, hardsigmoid); the gate
+    scales the project conv's input."""
     expand: Conv | None
     dw: Conv
     project: Conv
     residual: bool
+    se: tuple | None = None
 
     def to(self, device):
         return replace(self, expand=self.expand.to(device) if self.expand else None, dw=self.dw.to(device),
-                       project=self.project.to(device))
+                       project=self.project.to(device), se=tuple(c.to(device) for c in self.se) if self.se else None)
 
     @property
     def convs(self):
@@ -111,7 +117,7 @@ class MBlock:
 @dataclass
 class Program:
     name: str
-    kind: str                 # "resnet" | "alexnet" | "mobilenet"
+    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3"
     stem: Conv | None = None  # resnet
     blocks: list = field(default_factory=list)
     features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p))
@@ -146,6 +152,7 @@ class Program:
                 yield v
         for mb in self.mblocks:
             yield from mb.convs
+            yield from mb.se or ()
         if self.last is not None:
             yield self.last
         yield from self.fcs
@@ -533,17 +540,18 @@ def _dt(dtype: str) -> torch.dtype:
 
 
 def pack_dw_weight(w: torch.Tensor, dtype: str = "fp16") -> torch.Tensor:
-    """Depthwise [C, 1, 3, 3] -> tap-major [9, C] (tap = 3 kh + kw) in the
-    program's precision: a lane's 8 (fp16) / 4 (fp32) channels of one tap are
+    """Depthwise [C, 1, k, k], k 3 or 5 -> tap-major [k k, C] (tap = k kh + kw) in
+    the program's precision: a lane's 8 (fp16) / 4 (fp32) channels of one tap are
     one 16-byte load."""
-    if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
-        raise ValueError(f"depthwise weights must be [C, 1, 3, 3], got {tuple(w.shape)}")
-    return w.float().reshape(w.shape[0], 9).t().to(_dt(dtype)).contiguous()
+    if w.dim() != 4 or tuple(w.shape[1:]) not in ((1, 3, 3), (1, 5, 5)):
+        raise ValueError(f"depthwise weights must be [C, 1, 3, 3] or [C, 1, 5, 5], got {tuple(w.shape)}")
+    return w.float().reshape(w.shape[0], -1).t().to(_dt(dtype)).contiguous()
 
 
 def unpack_dw_weight(w9: torch.Tensor) -> torch.Tensor:
-    """Inverse of pack_dw_weight -> fp32 [C, 1, 3, 3]."""
-    return w9.float().t().reshape(w9.shape[1], 1, 3, 3).contiguous()
+    """Inverse of pack_dw_weight -> fp32 [C, 1, k, k]."""
+    k = 3 if w9.shape[0] == 9 else 5
+    return w9.float().t().reshape(w9.shape[1], 1, k, k).contiguous()
 
 
 def pw_kpad(k: int, dtype: str = "fp16") -> int:
@@ -569,13 +577,13 @@ def unpack_pw_weight(wp: torch.Tensor, k: int) -> torch.Tensor:
 
 
 def make_dw(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int, dtype: str = "fp16") -> Conv:
-    c = conv.in_channels
-    if conv.groups != c or conv.out_channels != c or conv.kernel_size != (3, 3) or conv.padding != (1, 1) \
-            or conv.stride[0] not in (1, 2) or c % 8:
-        raise ValueError(f"depthwise convs are 3x3 pad-1 stride-1/2 with C % 8 == 0, got {conv}")
+    c, k = conv.in_channels, conv.kernel_size[0]
+    if conv.groups != c or conv.out_channels != c or conv.kernel_size not in ((3, 3), (5, 5)) \
+            or conv.padding != (k // 2, k // 2) or conv.stride[0] not in (1, 2) or c % 8:
+        raise ValueError(f"depthwise convs are 3x3 pad-1 or 5x5 pad-2, stride 1/2, with C % 8 == 0, got {conv}")
     w, b = fold_bn(conv.weight, conv.bias, bn)
-    return Conv(w=pack_dw_weight(w, dtype), b=b.contiguous(), cin=c, cout=c, kh=3, kw=3, stride=conv.stride[0], pad=1,
-                relu=act != 0, groups=c, act=act, dw=True)
+    return Conv(w=pack_dw_weight(w, dtype), b=b.contiguous(), cin=c, cout=c, kh=k, kw=k, stride=conv.stride[0],
+                pad=k // 2, relu=act != 0, groups=c, act=act, dw=True)
 
 
 def make_pw(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int, dtype: str = "fp16") -> Conv:
@@ -713,6 +721,29 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
         p.fcs = [make_fc(m.classifier[1], False, dtype=dt)]
         p.num_classes = m.classifier[1].out_features
         return p
+    if isinstance(m, ref.MobileNetV3):
+        f = m.features
+        act_of = lambda seq: 3 if isinstance(seq[-1], nn.Hardswish) else 1 if isinstance(seq[-1], nn.ReLU) else 0
+        # the stem's hardswish is finished by its consumers (conv_dw act_in, conv1x1_narrow res_act): the
+        # small-C kernels stop at ReLU and run without activation here
+        p = Program(name, "mobilenet_v3", stem=make_conv(f[0][0], f[0][1], False, dt), dtype=dt)
+        p.stem.act = 3
+        for blk in list(f)[1:-1]:
+            mods = list(blk.block)
+            se = [mod for mod in mods if isinstance(mod, ref.SqueezeExcitation)]
+            seqs = [mod for mod in mods if isinstance(mod, nn.Sequential)]
+            expand = make_pw(seqs[0][0], seqs[0][1], act_of(seqs[0]), dt) if len(seqs) == 3 else None
+            p.mblocks.append(MBlock(expand, make_dw(seqs[-2][0], seqs[-2][1], act_of(seqs[-2]), dt),
+                                    make_pw(seqs[-1][0], seqs[-1][1], 0, dt), blk.use_res,
+                                    (make_pw(se[0].fc1, None, 1, dt), make_pw(se[0].fc2, None, 4, dt)) if se else None))
+        p.last = make_pw(f[-1][0], f[-1][1], 3, dt)
+        fc1, fc2 = m.classifier[0], m.classifier[3]
+        head = Conv(w=pack_pw_weight(fc1.weight.detach()[:, :, None, None], dt), b=fc1.bias.detach().float().contiguous(),
+                    cin=fc1.in_features, cout=fc1.out_features, kh=1, kw=1, stride=1, pad=0, relu=True, act=3,
+                    narrow=True)
+        p.fcs = [head, make_fc(fc2, False, dtype=dt)]
+        p.num_classes = fc2.out_features
+        return p
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
@@ -737,6 +768,8 @@ def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torc
     y = F.conv2d(x, unpack_conv_weight(c).to(x.device), c.b.to(x.device), c.stride, c.pad, groups=c.groups)
     if res is not None:
         y = y + res
+    if c.act >= 3:
+        return F.hardswish(y) if c.act == 3 else F.hardsigmoid(y)
     return y.clamp(0.0, 6.0) if c.act == 2 else F.relu(y) if c.act else y
 
 
@@ -744,6 +777,7 @@ def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torc
 def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
     """fp32 logits of the packed program on NCHW torch ops."""
     x = ref.preprocess_u8(img_u8)
+    fcs = p.fcs
     if p.kind == "resnet":
         x = F.max_pool2d(_emu_conv(p.stem, x), 3, 2, 1)
         for blk in p.blocks:
@@ -759,11 +793,21 @@ def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
             y = x if mb.expand is None else _emu_conv(mb.expand, x)
             x = _emu_conv(mb.project, _emu_conv(mb.dw, y), x if mb.residual else None)
         x = _emu_conv(p.last, x).mean(dim=(2, 3))
+    elif p.kind == "mobilenet_v3":
+        x = _emu_conv(p.stem, x)
+        for mb in p.mblocks:
+            y = _emu_conv(mb.dw, x if mb.expand is None else _emu_conv(mb.expand, x))
+            if mb.se is not None:
+                y = y * _emu_conv(mb.se[1], _emu_conv(mb.se[0], y.mean(dim=(2, 3), keepdim=True)))
+            x = _emu_conv(mb.project, y, x if mb.residual else None)
+        x = _emu_conv(p.last, x).mean(dim=(2, 3))
+        x = _emu_conv(p.fcs[0], x[:, :, None, None]).flatten(1)
+        fcs = p.fcs[1:]
     else:
         for k, v in p.features:
             x = _emu_conv(v, x) if k == "conv" else F.max_pool2d(x, *v)
         x = x.permute(0, 2, 3, 1).reshape(x.shape[0], -1)
-    for fc in p.fcs:
+    for fc in fcs:
         x = F.linear(x, fc.w.float().to(x.device), fc.b.to(x.device))
         if fc.relu:
             x = F.relu(x)
@@ -789,12 +833,13 @@ def program_flops(p: Program, hw: int = 224) -> float:
             if blk.down is not None:
                 hd = out_hw(hin, blk.down)
                 tot += hd * hd * blk.down.flops_per_out_pixel
-    elif p.kind == "mobilenet":
+    elif p.kind in ("mobilenet", "mobilenet_v3"):
         h = out_hw(hw, p.stem)
         tot += h * h * p.stem.flops_per_out_pixel
         for c in [c for mb in p.mblocks for c in mb.convs] + [p.last]:
             h = out_hw(h, c)
             tot += h * h * c.flops_per_out_pixel
+        tot += sum(c.flops_per_out_pixel for mb in p.mblocks for c in mb.se or ())   # SE FCs: one pixel an image
     else:
         h = hw
         for k, v in p.features:

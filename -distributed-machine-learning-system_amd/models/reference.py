@@ -192,6 +192,108 @@ def mobilenet_v2(num_classes=1000):
     return MobileNetV2(num_classes)
 
 
+def _make_divisible(v, divisor=8):
+    """torchvision's channel rounding: to the nearest multiple of ``divisor``, never below 90 % of ``v``."""
+    n = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return n + divisor if n < 0.9 * v else n
+
+
+def _conv_bn_act(cin, cout, k, s, groups, act):
+    """torchvision v0.10's ConvBNActivation as MobileNetV3 builds it: BN eps 0.001, momentum 0.01;
+    ``act`` is an activation class or None."""
+    layers = [_conv(cin, cout, k, s, (k - 1) // 2, groups), nn.BatchNorm2d(cout, eps=0.001, momentum=0.01)]
+    return nn.Sequential(*layers, *([act(inplace=True)] if act is not None else []))
+
+
+class SqueezeExcitation(nn.Module):
+    """torchvision v0.10's: x * hardsigmoid(fc2(relu(fc1(mean_hw(x))))), both FCs 1x1 convs with bias."""
+
+    def __init__(self, channels, squeeze_factor=4):
+        super().__init__()
+        squeeze = _make_divisible(channels // squeeze_factor, 8)
+        self.fc1 = nn.Conv2d(channels, squeeze, 1)
+        self.fc2 = nn.Conv2d(squeeze, channels, 1)
+
+    def forward(self, x):
+        scale = F.relu(self.fc1(x.mean(dim=(2, 3), keepdim=True)))
+        return F.hardsigmoid(self.fc2(scale)) * x
+
+
+class InvertedResidualV3(nn.Module):
+    """MobileNetV3 block: [1x1 expand-BN-act (absent when expanded == cin)], depthwise
+    k x k-BN-act, [SE], 1x1 project-BN; + x where stride 1 and cin == cout."""
+
+    def __init__(self, cin, k, expanded, cout, se, hs, stride):
+        super().__init__()
+        act = nn.Hardswish if hs else nn.ReLU
+        self.use_res = stride == 1 and cin == cout
+        layers = [_conv_bn_act(cin, expanded, 1, 1, 1, act)] if expanded != cin else []
+        layers.append(_conv_bn_act(expanded, expanded, k, stride, expanded, act))
+        if se:
+            layers.append(SqueezeExcitation(expanded))
+        layers.append(_conv_bn_act(expanded, cout, 1, 1, 1, None))
+        self.block = nn.Sequential(*layers)
+
+    def forward(self, x):
+        return x + self.block(x) if self.use_res else self.block(x)
+
+
+# (cin, kernel, expanded, cout, SE, hardswish (else ReLU), stride)
+MOBILENET_V3_SETTINGS = {
+    "large": ((16, 3, 16, 16, False, False, 1), (16, 3, 64, 24, False, False, 2), (24, 3, 72, 24, False, False, 1),
+              (24, 5, 72, 40, True, False, 2), (40, 5, 120, 40, True, False, 1), (40, 5, 120, 40, True, False, 1),
+              (40, 3, 240, 80, False, True, 2), (80, 3, 200, 80, False, True, 1), (80, 3, 184, 80, False, True, 1),
+              (80, 3, 184, 80, False, True, 1), (80, 3, 480, 112, True, True, 1), (112, 3, 672, 112, True, True, 1),
+              (112, 5, 672, 160, True, True, 2), (160, 5, 960, 160, True, True, 1), (160, 5, 960, 160, True, True, 1)),
+    "small": ((16, 3, 16, 16, True, False, 2), (16, 3, 72, 24, False, False, 2), (24, 3, 88, 24, False, False, 1),
+              (24, 5, 96, 40, True, True, 2), (40, 5, 240, 40, True, True, 1), (40, 5, 240, 40, True, True, 1),
+              (40, 5, 120, 48, True, True, 1), (48, 5, 144, 48, True, True, 1), (48, 5, 288, 96, True, True, 2),
+              (96, 5, 576, 96, True, True, 1), (96, 5, 576, 96, True, True, 1)),
+}
+MOBILENET_V3_LAST_CHANNEL = {"large": 1280, "small": 1024}
+
+
+class MobileNetV3(nn.Module):
+    """torchvision v0.10's mobilenet_v3_large (5,483,032 parameters) / mobilenet_v3_small
+    (2,542,856) at width 1.0."""
+
+    def __init__(self, arch, num_classes=1000):
+        super().__init__()
+        self.arch = arch
+        settings = MOBILENET_V3_SETTINGS[arch]
+        feats = [_conv_bn_act(3, settings[0][0], 3, 2, 1, nn.Hardswish)]
+        feats += [InvertedResidualV3(*row) for row in settings]
+        cin = settings[-1][3]
+        feats.append(_conv_bn_act(cin, 6 * cin, 1, 1, 1, nn.Hardswish))
+        self.features = nn.Sequential(*feats)
+        last = MOBILENET_V3_LAST_CHANNEL[arch]
+        self.classifier = nn.Sequential(nn.Linear(6 * cin, last), nn.Hardswish(inplace=True),
+                                        nn.Dropout(0.2, inplace=True), nn.Linear(last, num_classes))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out")
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, 0, 0.01)
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        x = self.features(x).mean(dim=(2, 3))
+        return self.classifier(x)
+
+
+def mobilenet_v3_large(num_classes=1000):
+    return MobileNetV3("large", num_classes)
+
+
+def mobilenet_v3_small(num_classes=1000):
+    return MobileNetV3("small", num_classes)
+
+
 def resnet18(num_classes=1000):
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes)
 
@@ -232,11 +334,12 @@ def alexnet(num_classes=1000):
     return AlexNet(num_classes)
 
 
-# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2
+# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2 / V3
 BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet,
             "resnet101": resnet101, "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d,
             "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
-            "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2}
+            "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2,
+            "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -294,7 +397,10 @@ ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18
            "resnet-50": "resnet50", "alex": "alexnet", "resnet-101": "resnet101", "resnet-152": "resnet152",
            "resnext50": "resnext50_32x4d", "resnext101": "resnext101_32x8d",
            "wide_resnet50": "wide_resnet50_2", "wide_resnet101": "wide_resnet101_2",
-           "mobilenet": "mobilenet_v2", "mobilenetv2": "mobilenet_v2", "mobilenet-v2": "mobilenet_v2"}
+           "mobilenet": "mobilenet_v2", "mobilenetv2": "mobilenet_v2", "mobilenet-v2": "mobilenet_v2",
+           "mobilenetv3_large": "mobilenet_v3_large", "mobilenet-v3-large": "mobilenet_v3_large",
+           "mobilenet_v3": "mobilenet_v3_large", "mobilenetv3_small": "mobilenet_v3_small",
+           "mobilenet-v3-small": "mobilenet_v3_small"}
 
 
 def canonical(name: str) -> str:

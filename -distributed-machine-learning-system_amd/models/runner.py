@@ -109,7 +109,7 @@ class HipRunner:
     GRAPH_SWITCHES = ("split", "split_front", "split_streams", "winograd", "wino_variant", "pack3", "pack3_f16",
                       "side_down", "stem_parts", "front_split", "fuse_stem", "batch_parts", "fuse_down",
                       "fuse_down_1x1", "fuse_next_1x1", "stem_u8", "route", "fuse_down_tail", "astem_form",
-                      "grouped_dense", "grouped_f32", "resize_u8")
+                      "grouped_dense", "grouped_f32", "resize_u8", "se_fused_pool", "se_fused_fc")
 
     def __init__(self, program: Program, device=None, fuse_stem: bool = True, front_split: int | None = None,
                  winograd: bool = True, wino_variant: int | None = None, pack3: bool = True):
@@ -206,7 +206,15 @@ class HipRunner:
         # pool, as before the uint8 kernel existed.  fp32 programs always take the uint8 kernel:
         # they refused such batches before.  (A/B: tools/ab_flag.py --attr resize_u8)
         self.resize_u8 = False
-        self.device = torch.device(device or "cuda")
+        # MobileNetV3's squeeze-and-excitation layers.  ``se_fused_pool``: the squeeze inside the
+        # depthwise launch (ops.conv_dw pool=) instead of ops.global_avgpool after it; measured
+        # slower on the sum of the SE layers in three of the four model x precision pairs (one
+        # workgroup an image leaves the 56 x 56 and 28 x 28 layers short of lanes), so off.
+        # ``se_fused_fc``: both FCs in one launch (ops.se_excite) instead of two
+        # ops.conv1x1_narrow launches; 2.1 - 2.5 x faster, so on.  docs/KERNELS.md has both A/Bs
+        self.se_fused_pool = False
+        self.se_fused_fc = True
+        self.device =torch.device(device or "cuda")
         self.p = program.to(self.device)
         self._graphs: dict[int, tuple] = {}
         # memory pool shared by this runner's captures (None: one private pool per
@@ -230,8 +238,8 @@ class HipRunner:
 
     # -- eager forward ------------------------------------------------------
     def _guarded(self) -> bool:
-        # MobileNetV2 has no split path (its fp32 program is true fp32), hence no range guard
-        return self.p.kind != "mobilenet" and self.p.dtype == "fp32" and self.split and self._split_ok()
+        # MobileNetV2 / V3 have no split path (their fp32 programs are true fp32), hence no range guard
+        return self.p.kind not in ("mobilenet", "mobilenet_v3") and self.p.dtype == "fp32" and self.split and self._split_ok()
 
     def logits(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
                start_offset: int = 0) -> torch.Tensor:
@@ -296,6 +304,8 @@ class HipRunner:
             return self._logits_in_parts(ims, parts)
         if p.kind == "mobilenet":
             return self._logits_mobilenet(ims, native)
+        if p.kind == "mobilenet_v3":
+            return self._logits_mobilenet_v3(ims, native)
         if p.dtype == "fp32":
             return self._logits_f32(ims, native)
         s = p.stem
@@ -363,6 +373,47 @@ class HipRunner:
         x = o.conv1x1_narrow(x, p.last.w, p.last.b, p.last.act)
         x = o.global_avgpool(x)
         return o.linear(x, p.fcs[0].w, p.fcs[0].b, relu=False, out_f32=True)
+
+    def _logits_mobilenet_v3(self, ims: _Images, native):
+        """MobileNetV3 large / small in either precision: NHWC4 producer -> small-C
+        stem conv WITHOUT activation (its hardswish is finished by the first block's
+        depthwise conv, act_in, and in V3-large by the first project conv's residual
+        read, res_act) -> per block narrow 1x1 expand, depthwise k x k, where
+        the block has an SE layer the spatial mean (ops.global_avgpool, or inside the
+        depthwise launch with ``se_fused_pool``) and the SE gate in one launch, narrow 1x1 project with the gate as its input scale (+ residual) ->
+        1x1 (hardswish) -> average pool -> classifier FC1 on the narrow kernel
+        (hardswish) -> FC2.  Everything on the current stream."""
+        o, p, s = self.ops, self.p, self.p.stem
+        f32 = p.dtype == "fp32"
+        x = self._nhwc4(ims, f32=f32) if native else o.resize_crop(ims.img, 256, 224)
+        x = o.conv2d(x, s.w, s.b, s.kh, s.kw, s.stride, s.pad, False)
+        for i, mb in enumerate(p.mblocks):
+            first, y, scale = i == 0, x, None
+            if mb.expand is not None:
+                y = o.conv1x1_narrow(y, mb.expand.w, mb.expand.b, mb.expand.act)
+            d = mb.dw
+            if mb.se is None:
+                y = o.conv_dw(y, d.w, d.b, d.kh, d.stride, d.act, act_in=3 if first else 0)
+            elif self.se_fused_pool:
+                mean = torch.empty(y.shape[0], d.cout, dtype=y.dtype, device=y.device)
+                y = o.conv_dw(y, d.w, d.b, d.kh, d.stride, d.act, act_in=3 if first else 0, pool=mean)
+            else:
+                y = o.conv_dw(y, d.w, d.b, d.kh, d.stride, d.act, act_in=3 if first else 0)
+                mean = o.global_avgpool(y)
+            if mb.se is not None:
+                fc1, fc2 = mb.se
+                if self.se_fused_fc:
+                    scale = o.se_excite(mean, fc1.w, fc1.b, fc2.w, fc2.b)
+                else:
+                    h = o.conv1x1_narrow(mean.view(-1, 1, 1, fc1.cin), fc1.w, fc1.b, fc1.act)
+                    scale = o.conv1x1_narrow(h, fc2.w, fc2.b, fc2.act).view(-1, fc2.cout)
+            x = o.conv1x1_narrow(y, mb.project.w, mb.project.b, mb.project.act, residual=x if mb.residual else None,
+                                 in_scale=scale, res_act=3 if first and mb.residual else 0)
+        x = o.conv1x1_narrow(x, p.last.w, p.last.b, p.last.act)
+        x = o.global_avgpool(x)
+        h = p.fcs[0]
+        x = o.conv1x1_narrow(x.view(-1, 1, 1, h.cin), h.w, h.b, h.act).view(-1, h.cout)
+        return o.linear(x, p.fcs[1].w, p.fcs[1].b, relu=False, out_f32=True)
 
     def _alex_stem_fusable(self, first, feats) -> bool:
         """conv1 has the fused-stem operands and ``feats`` (what follows it)

@@ -15,7 +15,7 @@ __all__ = [
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
-    "conv3x3_dw", "conv1x1_narrow",
+    "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -112,13 +112,36 @@ def conv3x3_dw(x, w9, bias, stride: int, act: int, clamp_in: bool = False, out=N
     return load().conv3x3_dw(x, w9, bias, int(stride), int(act), bool(clamp_in), out)
 
 
-def conv1x1_narrow(x, w, bias, act: int, residual=None, out=None):
+def conv1x1_narrow(x, w, bias, act: int, residual=None, out=None, in_scale=None, res_act: int = 0):
     """1x1 conv + bias (+ ``residual``, added before the activation) on NHWC
     [B, H, W, K] with K and N only multiples of 8 (<= 1280), fp16 or true fp32 by
     ``x``'s dtype (conv1x1_narrow.hip).  ``x`` may be a channel slice of a wider
     NHWC tensor.  ``w`` = models.packed.pack_pw_weight ([N, Kp], zero from K);
-    ``act`` 0 none, 1 ReLU, 2 ReLU6."""
-    return load().conv1x1_narrow(x, w, bias, int(act), residual, out)
+    ``act`` 0 none, 1 ReLU, 2 ReLU6, 3 hardswish, 4 hardsigmoid.  ``in_scale``
+    [B, K] (x's dtype): image b's pixels are multiplied by row b as they are read
+    (a squeeze-and-excitation gate; the product is rounded to x's dtype).
+    ``res_act`` 3: hardswish on the residual as it is read."""
+    return load().conv1x1_narrow(x, w, bias, int(act), residual, out, in_scale, int(res_act))
+
+
+def conv_dw(x, w, bias, k: int, stride: int, act: int, act_in: int = 0, pool=None, out=None):
+    """Depthwise k x k conv (k 3 or 5, pad k // 2, stride 1 or 2) + bias + activation
+    on NHWC [B, H, W, C], fp16 (C % 8 == 0) or fp32 (C % 4 == 0) by ``x``'s dtype
+    (conv_dw_kxk.hip; f32 accumulation).  ``w`` = models.packed.pack_dw_weight
+    ([k * k, C] tap-major, x's dtype), ``bias`` fp32 [C]; ``act`` 0 none, 1 ReLU, 2
+    ReLU6, 3 hardswish.  ``act_in`` 3 applies hardswish to the input: the hardswish
+    of a producer that has none.  ``pool`` ([B, C], x's dtype) also receives the
+    spatial mean of the output as stored, bit-identical from run to run (output
+    widths up to 256)."""
+    return load().conv_dw(x, w, bias, int(k), int(stride), int(act), int(act_in), pool, out)
+
+
+def se_excite(mean, w1, b1, w2, b2):
+    """Squeeze-and-excitation gate hardsigmoid(w2 relu(w1 mean + b1) + b2) of
+    ``mean`` [B, C] in one launch (se_excite.hip), fp16 or true fp32; ``w1`` [Csq,
+    Kp(C)] and ``w2`` [C, Kp(Csq)] = models.packed.pack_pw_weight, biases fp32;
+    C <= 1280, Csq <= 320, multiples of 8."""
+    return load().se_excite(mean, w1, b1, w2, b2)
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,
