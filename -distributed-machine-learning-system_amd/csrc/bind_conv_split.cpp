@@ -165,6 +165,40 @@ static torch::Tensor conv2d_split_impl(torch::Tensor x, torch::Tensor w, torch::
   return y;
 }
 
+// A ResNet basic block without downsample on split activations in one launch:
+// out = relu(scale_b * conv3x3(relu(scale_a * conv3x3(x, wa) + ba), wb) + bb + x), C = Cout = 64
+// (conv3x3_split_block.hip); bit-identical to conv2d_split(tile 50) twice.  grid > 0 caps the
+// persistent grid (tests: several bands per workgroup on small tensors).
+torch::Tensor conv3x3_split_block(torch::Tensor x, torch::Tensor wa, torch::Tensor ba, double scale_a, torch::Tensor wb,
+                                  torch::Tensor bb, double scale_b, int64_t grid) {
+  const auto dev = x.device();
+  check_operand(x, "x", torch::kHalf, 4, dev);
+  check_operand(wa, "wa", torch::kHalf, 2, dev);
+  check_operand(wb, "wb", torch::kHalf, 2, dev);
+  check_operand(ba, "ba", torch::kFloat, 1, dev);
+  check_operand(bb, "bb", torch::kFloat, 1, dev);
+  const int B = x.size(0), H = x.size(1), W = x.size(2), C2 = x.size(3);
+  TORCH_CHECK(C2 == 128 && wa.size(0) == 64 && wb.size(0) == 64 && wa.size(1) == 9 * 128 && wb.size(1) == 9 * 128 &&
+                  ba.size(0) == 64 && bb.size(0) == 64,
+              "conv3x3_split_block: a 64 -> 64 -> 64 block on split activations [B, H, W, 128]");
+  TORCH_CHECK(grid >= 0, "grid must be >= 0");
+  auto out = torch::empty_like(x);
+  if ((long)B * H * W == 0) return out;
+  TORCH_CHECK(conv3x3_split_c64_block_launch(hp(x), hp(wa), ba.data_ptr<float>(), (float)scale_a, hp(wb),
+                                             bb.data_ptr<float>(), (float)scale_b,
+                                             reinterpret_cast<half_t*>(out.data_ptr()), B, H, W, split_guard_for(dev),
+                                             cur_stream(), (int)grid),
+              "conv3x3_split_block: unsupported shape (49 <= W <= 56, 32-bit byte offsets)");
+  check_launch("conv3x3_split_block");
+  return out;
+}
+
+// whether the fused block kernel is supported AND the default for this batch
+bool conv3x3_split_block_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t Cout) {
+  return conv3x3_split_c64_block_supported((int)B, (int)H, (int)W, (int)C, (int)Cout) &&
+         conv3x3_split_c64_block_default((int)B, (int)H);
+}
+
 // Band-staged split 3x3/s1/p1 conv with an explicit persistent-grid cap (tests:
 // max_grid < tiles makes every workgroup run several tiles through one DMA ring).
 torch::Tensor conv3x3_band_split(torch::Tensor x, torch::Tensor w, torch::Tensor bias, c10::optional<torch::Tensor> res,

@@ -31,6 +31,9 @@ Tensor conv2d_split_dual(Tensor x, Tensor w, Tensor bias, int64_t KH, int64_t KW
 Tensor conv2d_split_tail(Tensor y, Tensor x2, Tensor w, Tensor bias, double acc_scale, int64_t stride2, bool relu,
                          int64_t tile);
 bool conv2d_split_tail_ok(int64_t B, int64_t Ho, int64_t Wo, int64_t C, int64_t Cx, int64_t Cout, int64_t mode);
+Tensor conv3x3_split_block(Tensor x, Tensor wa, Tensor ba, double scale_a, Tensor wb, Tensor bb, double scale_b,
+                           int64_t grid);
+bool conv3x3_split_block_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t Cout);
 Tensor conv1x1_dual_split(Tensor x1, Tensor x2, Tensor w, Tensor bias, double acc_scale, int64_t stride, bool relu);
 bool conv1x1_dual_split_ok(int64_t K1, int64_t K2, int64_t Cout, int64_t M);
 Tensor conv3x3_band_split(Tensor x, Tensor w, Tensor bias, OptTensor res, bool relu, double acc_scale, bool out_f32,
@@ -139,6 +142,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_split_tail_ok", &conv2d_split_tail_ok,
         "whether the K-tail fusion is the default for (B, Ho, Wo, C, Cx, Cout); mode 2: wherever supported, 3: not over the band kernel",
         py::arg("B"), py::arg("Ho"), py::arg("Wo"), py::arg("C"), py::arg("Cx"), py::arg("Cout"), py::arg("mode") = 1);
+  m.def("conv3x3_split_block", &conv3x3_split_block,
+        "a 64-channel split basic block (two 3x3/s1/p1 convs + ReLU, identity residual) in one row-streaming launch",
+        py::arg("x"), py::arg("wa"), py::arg("ba"), py::arg("scale_a"), py::arg("wb"), py::arg("bb"), py::arg("scale_b"),
+        py::arg("grid") = 0);
+  m.def("conv3x3_split_block_ok", &conv3x3_split_block_ok,
+        "whether the fused basic-block kernel is supported and the default for (B, H, W, C, Cout)",
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("C"), py::arg("Cout"));
   m.def("conv2d_pack3_split", &conv2d_pack3_split, "split-fp16 RGB stem conv on packed rows, fp32 out",
         py::arg("x3"), py::arg("w"), py::arg("bias"), py::arg("W"), py::arg("KH"), py::arg("KW"), py::arg("stride"),
         py::arg("pad"), py::arg("relu"), py::arg("acc_scale"), py::arg("tile") = -1);

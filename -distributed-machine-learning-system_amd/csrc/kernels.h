@@ -208,6 +208,14 @@ bool conv3x3_split_c64_supported(int H, int W, int C, int Cout);
 bool conv3x3_split_c64_launch(const half_t* x, const half_t* w, const float* bias, const half_t* res, half_t* y,
                               const void* zero, int B, int H, int W, int relu, float acc_scale, int* ovf,
                               hipStream_t st, int per_cu = 0);
+// one layer-1 basic block, relu(conv_b(relu(conv_a(x))) + x), in one row-streaming launch
+// (conv3x3_split_block.hip); _default: the batches that take it (two one-conv workgroups per CU);
+// max_grid > 0 caps the persistent grid (tests)
+bool conv3x3_split_c64_block_supported(int B, int H, int W, int C, int Cout);
+bool conv3x3_split_c64_block_default(int B, int H);
+bool conv3x3_split_c64_block_launch(const half_t* x, const half_t* wa, const float* ba, float scale_a, const half_t* wb,
+                                    const float* bb, float scale_b, half_t* out, int B, int H, int W, int* ovf,
+                                    hipStream_t st, int max_grid = 0);
 // band-staged 3x3/s1/p1 conv (conv3x3_band.hip): ResNet layers 2-4 (W 28 / 14 / 7,
 // C % 64 == 0, Cout % 128 == 0); x / res read in place at pixel strides ldx / ldr (halfs).
 // Split operands by default; f16: plain fp16 operands, weights [Cout][9*C], fp16 output.

@@ -27,100 +27,9 @@
 // (flattened image-major), as one band per image it touches, so every
 // workgroup finishes within a row of the others (round 4: 8-row bands, 2800
 // items over 512 workgroups = 5.47 rounds, the last one half empty).
-#include "../kernels.h"
-#include "../launch_util.h"
+#include "conv3x3_split_c64.h"
 
 namespace idunno {
-
-namespace c64s {
-constexpr int C = 64;              // channels in and out
-constexpr int PIX = 2 * C;         // halfs per pixel (split)
-constexpr int RC = 60;             // LDS columns per ring row (W + 2 <= 58 read; 60 = 3.75 whole DMA instructions)
-constexpr int RB = RC * 256;       // bytes per ring row
-constexpr int RING = 5;            // rows y-2 .. y+1 in use (a row pair's tail fragment) + row y+2 landing
-constexpr int BIAS = RING * RB;    // the 64 biases (fp32), read by the epilogue: no VGPRs held for them
-constexpr int LDS = BIAS + 256;    // 77,056 B: 2 workgroups per CU
-constexpr int WMAX = 56;           // 3 full fragments + an 8-column tail per row
-constexpr int NST = 3;             // epilogue stores per wave and row, at least (3 fragments, 16 B a lane)
-}  // namespace c64s
-
-struct C64sArgs {
-  const half_t* x;      // split [B][H][W][128]
-  const half_t* w;      // split weights [64][9 * 128] (pack_split_weight)
-  const float* bias;    // [64]
-  const half_t* res;    // split [B][H][W][128] or nullptr
-  half_t* y;            // split [B][H][W][128]
-  const void* zero;     // unused (padding comes from out-of-range buffer offsets)
-  int B, H, W, relu, nrows;
-  float acc_scale;
-  int* ovf;             // split range guard flag or nullptr (common.h split_guard)
-};
-
-__device__ __forceinline__ int c64s_slot(int chunk, int col) { return chunk ^ ((2 * col) & 15); }
-
-// ds_read_b128 with an immediate byte offset (invisible to the wait-count pass, see common.h)
-template <int OFF>
-__device__ __forceinline__ half8v lds_read_b128_off(uint32_t addr) {
-  static_assert(OFF >= 0 && OFF < 65536, "ds offset range");
-  half8v v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-
-// fragment f's read (f = 0..2 of the row: immediate offset 4096 * f; f = 3: the
-// tail fragment, whose lanes carry their own row base)
-__device__ __forceinline__ half8v lds_read_frag(uint32_t addr, int f) {
-  switch (f) {
-    case 0: return lds_read_b128_off<0>(addr);
-    case 1: return lds_read_b128_off<4096>(addr);
-    case 2: return lds_read_b128_off<8192>(addr);
-    default: return lds_read_b128_off<0>(addr);
-  }
-}
-
-// Per-lane buffer offsets of the row DMA (constant for the launch): chunk
-// i = r * 256 + tid of an LDS ring row is column i / 16, slot i % 16, which holds
-// global chunk c64s_slot(slot, col) of pixel col - 1; padding columns get an
-// offset past the descriptor (zeros).
-__device__ __forceinline__ void c64s_row_offsets(const C64sArgs& a, int tid, uint32_t (&voff)[4]) {
-  using namespace c64s;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i = r * 256 + tid;
-    const int col = i >> 4, slot = i & 15;
-    const int ix = col - 1;
-    voff[r] = (unsigned)ix < (unsigned)a.W ? (uint32_t)(ix * 256 + (c64s_slot(slot, col) << 4)) : 0x80000000u;
-  }
-}
-
-// DMA input row iy of image b into ring slot rs (zeros outside the image):
-// RC * 16 = 960 chunks, so waves 0-2 issue 4 DMA instructions and wave 3 issues 3
-// (a wave-uniform split: the counted waits below only need each wave's own DMAs
-// to be older than its epilogue stores).  The row's base is the uniform soffset.
-template <typename Rsrc>
-__device__ __forceinline__ void c64s_load_row(const C64sArgs& a, char* ring, Rsrc x_rsrc, const uint32_t (&voff)[4],
-                                              int b, int iy, int rs, int tid) {
-  using namespace c64s;
-  const bool rowv = (unsigned)iy < (unsigned)a.H;
-  const int soff = rowv ? (b * a.H + iy) * a.W * 256 : 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (r == 3 && (tid >> 6) == 3) break;       // chunks 960..1023: past the row (wave-uniform)
-    dma_buf16(x_rsrc, ring + rs * RB + (r * 256 + (tid & ~63)) * 16, rowv ? voff[r] : 0x80000000u, soff);
-  }
-}
-
-// D groups of B reads in the register ring: D - 1 groups in flight behind the
-// group whose MFMAs issue
-template <int N>
-__device__ __forceinline__ void c64s_wait_groups() {
-  lds_waitcnt<2 * N>();
-}
-
-template <int N>
-struct c64s_nf {
-  static constexpr int value = N;
-};
 
 // Output row y is fragments 0-2 (columns 0..47) plus, every second row, one
 // TAIL fragment holding columns 48..W-1 of BOTH rows of the pair (lanes 0-7:
@@ -157,7 +66,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_c64_kernel(const C64sArg
   const uint32_t ring = lds_addr(smem);
   const auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, 0x7fffffff, 0x00020000);
   uint32_t voff[4];
-  c64s_row_offsets(a, tid, voff);
+  c64s_row_offsets<256>(a.W, tid, voff);
   // per-lane LDS byte offset of column col0 + kw, chunk 4c + q:
   //   col*256 + (slot << 4), slot = (4c + q) ^ x, x = (2*col) & 15
   // = off ^ (c << 6): bits 6-7 hold c ^ (x >> 2), bits 4-5 q ^ (x & 3)
@@ -182,9 +91,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_c64_kernel(const C64sArg
     r += y1 - y0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();              // previous item's ring reads are done
-    c64s_load_row(a, smem, x_rsrc, voff, b, y0 - 1, (y0 + 4) % RING, tid);
-    c64s_load_row(a, smem, x_rsrc, voff, b, y0, y0 % RING, tid);
-    c64s_load_row(a, smem, x_rsrc, voff, b, y0 + 1, (y0 + 1) % RING, tid);
+    c64s_load_row<256>(smem, x_rsrc, voff, a.H, a.W, b, y0 - 1, (y0 + 4) % RING, tid);
+    c64s_load_row<256>(smem, x_rsrc, voff, a.H, a.W, b, y0, y0 % RING, tid);
+    c64s_load_row<256>(smem, x_rsrc, voff, a.H, a.W, b, y0 + 1, (y0 + 1) % RING, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     for (int y = y0; y < y1; ++y) {
       // row y+1 landed: its DMA (issued one row ago) is older than this wave's
@@ -192,7 +101,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_c64_kernel(const C64sArg
       // and ends every wave's reads of row y-3, whose slot row y+2 now takes
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST) : "memory");
       __builtin_amdgcn_s_barrier();
-      if (y + 2 <= y1) c64s_load_row(a, smem, x_rsrc, voff, b, y + 2, (y + 2) % RING, tid);
+      if (y + 2 <= y1) c64s_load_row<256>(smem, x_rsrc, voff, a.H, a.W, b, y + 2, (y + 2) % RING, tid);
       const bool pair = ((y - y0) & 1) != 0;           // tail of rows (y-1, y)
       const bool single = !pair && y == y1 - 1;        // odd band: tail of row y alone
       // the tail's rows per lane: lanes 0-7 the pair's first row, 8-15 the second

@@ -109,7 +109,7 @@ class HipRunner:
     GRAPH_SWITCHES = ("split", "split_front", "split_streams", "winograd", "wino_variant", "pack3", "pack3_f16",
                       "side_down", "stem_parts", "front_split", "fuse_stem", "batch_parts", "fuse_down",
                       "fuse_down_1x1", "fuse_next_1x1", "stem_u8", "route", "fuse_down_tail", "astem_form",
-                      "grouped_dense", "grouped_f32", "resize_u8", "se_fused_pool", "se_fused_fc")
+                      "grouped_dense", "grouped_f32", "resize_u8", "se_fused_pool", "se_fused_fc", "fuse_block_c64")
 
     def __init__(self, program: Program, device=None, fuse_stem: bool = True, front_split: int | None = None,
                  winograd: bool = True, wino_variant: int | None = None, pack3: bool = True):
@@ -174,6 +174,11 @@ class HipRunner:
         # downsample (A/B arm).  ResNet18 b400 +3.2 %, b50 +1.8 % (docs/KERNELS.md)
         self.fuse_down_tail = 1
         self._tail: dict = {}
+        # split path: a 64-channel basic block without downsample (ResNet18/34 layer 1) as ONE
+        # row-streaming launch (ops.conv3x3_split_block: the first conv's output stays in LDS).
+        # 0: the two conv launches; 1: fused where ops.conv3x3_split_block_ok says so.
+        # Bit-identical outputs (A/B: tools/ab_flag.py --attr fuse_block_c64 --values 0,1)
+        self.fuse_block_c64 = 1
         # fp16 bottleneck blocks with a 1x1 downsample: the expansion 1x1 and the
         # downsample as ONE GEMM over [y | x] (ops.conv1x1_dual), so the
         # downsample's output (the residual) never reaches HBM
@@ -764,6 +769,9 @@ class HipRunner:
             y = self._conv_split(c0, x)
             w, b, scale = self._tail_weights(blk)
             return self.ops.conv2d_split_tail(y, x, w, b, scale, d.stride, c1.relu)
+        if not last and out is None and self._block_c64_ok(blk, x):
+            ca, cb = blk.convs
+            return self.ops.conv3x3_split_block(x, ca.sw, ca.b, ca.s_scale, cb.sw, cb.b, cb.s_scale)
         if not last and out is None and self._dual1_split_ok(blk, x):
             y = x
             for c in blk.convs[:-1]:
@@ -775,6 +783,18 @@ class HipRunner:
         for c in blk.convs[:-1]:
             y = self._conv_split(c, y)
         return self._conv_split(blk.convs[-1], y, residual=idt, out_f32=last, out=out)
+
+    def _block_c64_ok(self, blk, x) -> bool:
+        """A basic block without downsample, two 3x3/1/pad-1 convs with ReLU, whose shape
+        the library fuses by default (fuse_block_c64); ``route`` bit 1 keeps it unfused."""
+        if not (int(self.fuse_block_c64) and blk.down is None and len(blk.convs) == 2 and x.is_cuda
+                and not (self.route & 2)):
+            return False
+        ok = all(c.kh == c.kw == 3 and c.stride == 1 and c.pad == 1 and c.relu and c.groups == 1
+                 and c.sw is not None for c in blk.convs)
+        ca, cb = blk.convs
+        return ok and ca.cout == cb.cin and x.shape[3] == 2 * ca.cin and \
+            self.ops.conv3x3_split_block_ok(x.shape[0], x.shape[1], x.shape[2], ca.cin, cb.cout)
 
     def _tail_ok(self, blk, x) -> bool:
         """A basic block (two 3x3 convs) with a 1x1 pad-0 downsample whose shape

@@ -16,7 +16,7 @@ __all__ = [
     "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
     "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite",
-    "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
+    "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "conv3x3_split_block", "conv3x3_split_block_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
     "JPEG_PAR_SUB_BITS", "JPEG_PAR_THREADS", "JPEG_PAR_MAX_ROUNDS",
@@ -71,6 +71,22 @@ def conv2d_split_tail_ok(b: int, ho: int, wo: int, c: int, cx: int, cout: int, m
     arm); 3: the rule, but not where the band kernel is the unfused default
     (W 28: the other arm of the layer-2 A/B); 0: never."""
     return bool(load().conv2d_split_tail_ok(b, ho, wo, c, cx, cout, mode))
+
+
+def conv3x3_split_block(x, wa, ba, scale_a: float, wb, bb, scale_b: float, grid: int = 0):
+    """A ResNet basic block without downsample on split activations [B, H, W, 128]
+    in ONE launch: relu(conv_b(relu(conv_a(x))) + x), both convs 3x3 / stride 1 /
+    pad 1, 64 -> 64 (conv3x3_split_block.hip: the intermediate stays in LDS).
+    Bit-identical to ``conv2d_split(..., tile=50)`` twice.  49 <= W <= 56.
+    ``grid`` > 0 caps the persistent grid (tests)."""
+    return load().conv3x3_split_block(x, wa, ba, scale_a, wb, bb, scale_b, grid)
+
+
+def conv3x3_split_block_ok(b: int, h: int, w: int, c: int, cout: int) -> bool:
+    """Whether ``conv3x3_split_block`` is supported AND the default for this
+    shape: C = Cout = 64, 49 <= W <= 56, 32-bit byte offsets, and B * H >= 16 rows
+    per CU (below that the one-conv kernel runs one workgroup per CU and stays)."""
+    return bool(load().conv3x3_split_block_ok(b, h, w, c, cout))
 
 
 def conv3x3_grouped(x, w, bias, groups: int, stride: int, relu: bool):
