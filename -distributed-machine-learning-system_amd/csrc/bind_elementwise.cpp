@@ -18,11 +18,24 @@ static bool check_pool_input(const torch::Tensor& x) {
   return f32;
 }
 
-torch::Tensor maxpool2d_nhwc(torch::Tensor x, int64_t k, int64_t s, int64_t pad, c10::optional<torch::Tensor> out) {
+// Output extent of a pool: floor((n + 2 pad - k) / s) + 1, or with ceil_mode PyTorch's rule: the ceiling, less one
+// where the last window would start at or past n + pad (in the right padding).  The kernels clip every window to
+// the input, so a clipped last window needs nothing else.
+static int pool_out_size(int n, int k, int s, int pad, bool ceil_mode) {
+  if (!ceil_mode) return (n + 2 * pad - k) / s + 1;
+  if (n + 2 * pad < k) return 0;
+  int o = (n + 2 * pad - k + s - 1) / s + 1;
+  if ((o - 1) * s >= n + pad) --o;
+  return o;
+}
+
+torch::Tensor maxpool2d_nhwc(torch::Tensor x, int64_t k, int64_t s, int64_t pad, c10::optional<torch::Tensor> out,
+                             bool ceil_mode) {
   const bool f32 = check_pool_input(x);
   TORCH_CHECK(k >= 1 && s >= 1 && pad >= 0 && 2 * pad <= k, "bad pool geometry");
   const int B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  const int Ho = (H + 2 * pad - k) / s + 1, Wo = (W + 2 * pad - k) / s + 1;
+  const int Ho = pool_out_size(H, (int)k, (int)s, (int)pad, ceil_mode);
+  const int Wo = pool_out_size(W, (int)k, (int)s, (int)pad, ceil_mode);
   TORCH_CHECK(Ho > 0 && Wo > 0, "empty output");
   auto y = optional_out(out, x.device(), x.scalar_type(), {B, Ho, Wo, C});
   if (!B) return y;

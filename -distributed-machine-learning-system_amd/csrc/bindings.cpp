@@ -56,6 +56,10 @@ Tensor conv1x1_narrow(Tensor x, Tensor w, Tensor bias, int64_t act, OptTensor re
 Tensor conv_dw(Tensor x, Tensor w, Tensor bias, int64_t k, int64_t stride, int64_t act, int64_t act_in, OptTensor pool,
                OptTensor out);
 Tensor se_excite(Tensor mean, Tensor w1, Tensor b1, Tensor w2, Tensor b2);
+// bind_fire.cpp
+Tensor fire(Tensor x, Tensor ws, Tensor bs, Tensor we, Tensor be, int64_t e1, OptTensor out);
+bool fire_ok_py(int64_t H, int64_t W, int64_t Cin, int64_t S, int64_t E1, int64_t E3);
+Tensor conv1x1_relu_pool(Tensor x, Tensor w, Tensor bias);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -90,7 +94,7 @@ Tensor float_to_nhwc4(Tensor x, bool f32);
 Tensor float_to_pack3(Tensor x, int64_t KW, int64_t stride, int64_t pad, bool f16);
 Tensor float_to_pack3_split(Tensor x, int64_t KW, int64_t stride, int64_t pad);
 // bind_elementwise.cpp
-Tensor maxpool2d_nhwc(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out);
+Tensor maxpool2d_nhwc(Tensor x, int64_t k, int64_t s, int64_t pad, OptTensor out, bool ceil_mode);
 Tensor global_avgpool_nhwc(Tensor x);
 Tensor resize_crop_u8(Tensor img, int64_t resize, int64_t crop, OptTensor out);
 py::dict resize_u8_plan(int64_t Hi, int64_t Wi, int64_t resize, int64_t crop);
@@ -211,6 +215,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act_in") = 0, py::arg("pool") = py::none(), py::arg("out") = py::none());
   m.def("se_excite", &se_excite, "hardsigmoid(w2 relu(w1 mean + b1) + b2) in one launch, fp16 or fp32",
         py::arg("mean"), py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"));
+  m.def("fire", &fire,
+        "SqueezeNet Fire module in one launch: concat(relu(1x1), relu(3x3 pad 1)) of s = relu(1x1(x)), fp16 or fp32 "
+        "NHWC; the squeeze map stays in LDS",
+        py::arg("x"), py::arg("ws"), py::arg("bs"), py::arg("we"), py::arg("be"), py::arg("e1"),
+        py::arg("out") = py::none());
+  m.def("fire_ok", &fire_ok_py, "whether the Fire kernel takes (H, W, Cin, S, E1, E3) in both precisions");
+  m.def("fire_kpad", [](int64_t S, bool f32) { return (int64_t)fire_kpad((int)S, f32); },
+        "row length of fire's expand weights for S squeeze channels", py::arg("S"), py::arg("f32"));
+  m.def("fire_max_w", []() { return (int64_t)fire_max_w(); }, "widest image the Fire kernel takes");
+  m.def("conv1x1_relu_pool", &conv1x1_relu_pool,
+        "mean over pixels of relu(1x1 conv + bias): fp32 [B, N] from fp16 or fp32 NHWC, bit-stable", py::arg("x"),
+        py::arg("w"), py::arg("bias"));
   m.def("conv1x1_narrow_kpad", [](int64_t K, bool f32) { return (int64_t)conv1x1_narrow_kpad((int)K, f32); },
         "row length of conv1x1_narrow's weights for K input channels", py::arg("K"), py::arg("f32"));
   m.def("pick_tile_split", &pick_tile_split, "split conv tile heuristic for (M, Cout)");
@@ -254,7 +270,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "host only: resize_crop_u8's launch plan and fixed-point tables (bh, kh, bv, kv) for one geometry",
         py::arg("Hi"), py::arg("Wi"), py::arg("resize"), py::arg("crop"));
   m.def("maxpool2d_nhwc", &maxpool2d_nhwc, "NHWC max pool (into ``out`` when given)", py::arg("x"), py::arg("k"),
-        py::arg("s"), py::arg("pad"), py::arg("out") = py::none());
+        py::arg("s"), py::arg("pad"), py::arg("out") = py::none(), py::arg("ceil_mode") = false);
   m.def("global_avgpool_nhwc", &global_avgpool_nhwc, "NHWC global average pool");
   m.def("softmax_top1", &softmax_top1, "fused row softmax + argmax; a set ``ovf`` flag marks every row -2",
         py::arg("logits"), py::arg("packed") = py::none(), py::arg("ovf") = py::none());

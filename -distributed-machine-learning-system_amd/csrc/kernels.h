@@ -322,6 +322,21 @@ bool conv_dw_pool_ok(int Wo);
 bool se_excite_launch(const void* mean, const void* w1, const float* b1, const void* w2, const float* b2, void* scale,
                       int B, int C, int Csq, bool f32, hipStream_t st);
 
+// ---- SqueezeNet: fire.hip ----
+// y[B, H, W, E1 + E3] = concat(relu(W1 s + b1), relu(W3 (*)3x3 pad 1 s + b3)), s = relu(Ws x + bs), in one launch; x, y
+// and the weights fp16, or fp32 with f32.  ws [S, conv1x1_narrow_kpad(Cin)], we [E1 + E3, fire_kpad(S)] (models/packed.py
+// pack_fire_weights), biases fp32.  fire_ok: Cin % 16 == 0 <= 512, S 16 | 32 | 48 | 64, E1 and E3 % 16 == 0 <= 256,
+// W <= fire_max_w().  False: unsupported shape, nothing launched.
+bool fire_launch(const void* x, const void* ws, const float* bs, const void* we, const float* be, void* y, int B, int H,
+                 int W, int Cin, int S, int E1, int E3, bool f32, hipStream_t st);
+bool fire_ok(int H, int W, int Cin, int S, int E1, int E3, bool f32);
+int fire_kpad(int S, bool f32);
+int fire_max_w();
+// out[B, N] (fp32) = mean over the HW pixels of relu(x[B, HW, K] w[N, Kp]^T + bias), w as conv1x1_narrow's; K, N
+// multiples of 8, <= 1280; the same bits every run.  False: unsupported shape, nothing launched.
+bool conv1x1_pool_launch(const void* x, const void* w, const float* bias, float* out, int B, int HW, int K, int N,
+                         bool f32, hipStream_t st);
+
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.

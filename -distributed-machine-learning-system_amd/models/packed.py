@@ -19,6 +19,8 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
     (pack_pw_weight); both in the program's precision, true fp32 for dtype "fp32"
   * MobileNetV3: the same two forms (depthwise 5x5 -> [25, C]); the squeeze-and-
     excitation FCs and the classifier's first Linear are pointwise weights too
+  * SqueezeNet: a Fire module's squeeze as a pointwise weight and both expands as ONE
+    [E1 + E3, Kp(9 S)] tap-major weight (pack_fire_weights, fire.hip), the head conv pointwise
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -115,12 +117,35 @@ class MBlock:
 
 
 @dataclass
+class Fire:
+    """SqueezeNet Fire module for ops.fire: ``squeeze`` a pointwise Conv (ReLU), ``we`` / ``be`` both expand
+    convs (pack_fire_weights: rows [0, e1) the 1x1, the rest the 3x3; biases in that order), ``s`` squeeze width."""
+    squeeze: Conv
+    we: torch.Tensor
+    be: torch.Tensor
+    e1: int
+    e3: int
+
+    def to(self, device):
+        return replace(self, squeeze=self.squeeze.to(device), we=self.we.to(device), be=self.be.to(device))
+
+    @property
+    def s(self) -> int:
+        return self.squeeze.cout
+
+    @property
+    def flops_per_out_pixel(self) -> int:
+        return self.squeeze.flops_per_out_pixel + 2 * self.s * (self.e1 + 9 * self.e3)
+
+
+@dataclass
 class Program:
     name: str
-    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3"
+    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3" | "squeezenet"
     stem: Conv | None = None  # resnet
     blocks: list = field(default_factory=list)
-    features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p))
+    features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p)); squeezenet, between
+    #                                               ``stem`` and ``last`` (the head conv): ("fire", Fire) | ("pool", (3, 2, 0))
     mblocks: list = field(default_factory=list)   # mobilenet: list[MBlock] between ``stem`` and ``last``
     last: Conv | None = None                      # mobilenet: the 1x1 before the pool
     fcs: list = field(default_factory=list)       # list[Conv] as 1x1 convs (last -> fp32 logits)
@@ -130,7 +155,7 @@ class Program:
     def to(self, device):
         return replace(self, stem=self.stem.to(device) if self.stem else None,
                        blocks=[b.to(device) for b in self.blocks],
-                       features=[(k, v.to(device) if k == "conv" else v) for k, v in self.features],
+                       features=[(k, v if k == "pool" else v.to(device)) for k, v in self.features],
                        mblocks=[b.to(device) for b in self.mblocks], last=self.last.to(device) if self.last else None,
                        fcs=[f.to(device) for f in self.fcs])
 
@@ -138,6 +163,9 @@ class Program:
         tot = 0
         for c in self.all_convs():
             tot += c.w.numel() * c.w.element_size() + c.b.numel() * 4
+        for k, v in self.features:
+            if k == "fire":                   # the expands as stored: the 1x1's rows are as long as the 3x3's
+                tot += v.we.numel() * v.we.element_size() + v.be.numel() * 4
         return tot
 
     def all_convs(self):
@@ -150,6 +178,8 @@ class Program:
         for k, v in self.features:
             if k == "conv":
                 yield v
+            elif k == "fire":                 # its expands are one packed tensor (Fire.we), not Convs
+                yield v.squeeze
         for mb in self.mblocks:
             yield from mb.convs
             yield from mb.se or ()
@@ -594,6 +624,51 @@ def make_pw(conv: nn.Conv2d, bn: nn.BatchNorm2d | None, act: int, dtype: str = "
                 stride=1, pad=0, relu=act != 0, act=act, narrow=True)
 
 
+# ---------------------------------------------------------------------------
+# SqueezeNet Fire modules (fire.hip)
+# ---------------------------------------------------------------------------
+
+FIRE_S = (16, 32, 48, 64)
+
+
+def fire_kpad(s: int, dtype: str = "fp16") -> int:
+    """Row length of a Fire module's expand weights: 9 S up to the kernel's K step."""
+    return pw_kpad(9 * s, dtype)
+
+
+def pack_fire_weights(w1: torch.Tensor, w3: torch.Tensor, dtype: str = "fp16") -> torch.Tensor:
+    """Expand convs [E1, S, 1, 1] and [E3, S, 3, 3] -> [E1 + E3, Kp] in the program's precision, the K axis
+    tap-major (k = (3 kh + kw) S + c) and zero from 9 S to Kp = fire_kpad(S): the 3x3's rows are its weights,
+    the 1x1's rows hold theirs in the centre tap's slice [4 S, 5 S) and zeros elsewhere (the kernel walks only
+    that slice for them)."""
+    e1, s = w1.shape[:2]
+    e3 = w3.shape[0]
+    if w1.dim() != 4 or w3.dim() != 4 or tuple(w1.shape[2:]) != (1, 1) or tuple(w3.shape[1:]) != (s, 3, 3):
+        raise ValueError(f"fire weights must be [E1, S, 1, 1] and [E3, S, 3, 3], got {tuple(w1.shape)}, {tuple(w3.shape)}")
+    if s not in FIRE_S or e1 % 16 or e3 % 16 or not 0 < e1 <= 256 or not 0 < e3 <= 256:
+        raise ValueError(f"fire: S must be one of {FIRE_S} and E1, E3 multiples of 16 up to 256, got S={s}, E1={e1}, "
+                         f"E3={e3}")
+    p = torch.zeros(e1 + e3, fire_kpad(s, dtype), dtype=_dt(dtype))
+    p[:e1, 4 * s:5 * s] = w1.float().reshape(e1, s).to(p.dtype)
+    p[e1:, :9 * s] = w3.float().permute(0, 2, 3, 1).reshape(e3, 9 * s).to(p.dtype)
+    return p
+
+
+def unpack_fire_weights(we: torch.Tensor, e1: int, s: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of pack_fire_weights -> fp32 ([E1, S, 1, 1], [E3, S, 3, 3])."""
+    w1 = we[:e1, 4 * s:5 * s].float().reshape(e1, s, 1, 1).contiguous()
+    w3 = we[e1:, :9 * s].float().reshape(-1, 3, 3, s).permute(0, 3, 1, 2).contiguous()
+    return w1, w3
+
+
+def make_fire(f: "ref.Fire", dtype: str = "fp16") -> Fire:
+    if f.squeeze.in_channels % 16 or f.squeeze.in_channels > 512:
+        raise ValueError(f"fire: Cin must be a multiple of 16 up to 512, got {f.squeeze.in_channels}")
+    we = pack_fire_weights(f.expand1x1.weight.detach(), f.expand3x3.weight.detach(), dtype)
+    be = torch.cat([f.expand1x1.bias.detach(), f.expand3x3.bias.detach()]).float().contiguous()
+    return Fire(make_pw(f.squeeze, None, 1, dtype), we, be, f.expand1x1.out_channels, f.expand3x3.out_channels)
+
+
 # Winograd F(2x2, 3x3) filter transform (Lavin & Gray): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
@@ -744,6 +819,19 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
         p.fcs = [head, make_fc(fc2, False, dtype=dt)]
         p.num_classes = fc2.out_features
         return p
+    if isinstance(m, ref.SqueezeNet):
+        f = list(m.features)
+        p = Program(name, "squeezenet", stem=make_conv(f[0], None, True, dt), dtype=dt)
+        for mod in f[2:]:
+            if isinstance(mod, ref.Fire):
+                p.features.append(("fire", make_fire(mod, dt)))
+            elif isinstance(mod, nn.MaxPool2d) and mod.ceil_mode:
+                p.features.append(("pool", (mod.kernel_size, mod.stride, mod.padding)))
+            else:
+                raise TypeError(f"cannot compile {mod} in a SqueezeNet")
+        p.last = make_pw(m.classifier[1], None, 1, dt)      # the head: ops.conv1x1_relu_pool -> fp32 logits
+        p.num_classes = m.classifier[1].out_channels
+        return p
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
@@ -763,6 +851,13 @@ def build_program(name: str, seed: int = 0, randomize_bn: bool = False, dtype: s
 # ---------------------------------------------------------------------------
 # fp32 torch emulation of a packed program (CPU-testable)
 # ---------------------------------------------------------------------------
+
+def _emu_fire(f: Fire, x: torch.Tensor) -> torch.Tensor:
+    w1, w3 = unpack_fire_weights(f.we, f.e1, f.s)
+    s = _emu_conv(f.squeeze, x)
+    return torch.cat([F.relu(F.conv2d(s, w1.to(x.device), f.be[:f.e1].to(x.device))),
+                      F.relu(F.conv2d(s, w3.to(x.device), f.be[f.e1:].to(x.device), padding=1))], 1)
+
 
 def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torch.Tensor:
     y = F.conv2d(x, unpack_conv_weight(c).to(x.device), c.b.to(x.device), c.stride, c.pad, groups=c.groups)
@@ -803,6 +898,11 @@ def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
         x = _emu_conv(p.last, x).mean(dim=(2, 3))
         x = _emu_conv(p.fcs[0], x[:, :, None, None]).flatten(1)
         fcs = p.fcs[1:]
+    elif p.kind == "squeezenet":
+        x = _emu_conv(p.stem, x)
+        for k, v in p.features:
+            x = _emu_fire(v, x) if k == "fire" else F.max_pool2d(x, *v, ceil_mode=True)
+        x = _emu_conv(p.last, x).mean(dim=(2, 3))
     else:
         for k, v in p.features:
             x = _emu_conv(v, x) if k == "conv" else F.max_pool2d(x, *v)
@@ -840,6 +940,15 @@ def program_flops(p: Program, hw: int = 224) -> float:
             h = out_hw(h, c)
             tot += h * h * c.flops_per_out_pixel
         tot += sum(c.flops_per_out_pixel for mb in p.mblocks for c in mb.se or ())   # SE FCs: one pixel an image
+    elif p.kind == "squeezenet":
+        h = out_hw(hw, p.stem)
+        tot += h * h * p.stem.flops_per_out_pixel
+        for k, v in p.features:
+            if k == "fire":
+                tot += h * h * v.flops_per_out_pixel
+            else:
+                h = -(-(h + 2 * v[2] - v[0]) // v[1]) + 1      # ceil mode (no window starts in the padding: pad 0)
+        tot += h * h * p.last.flops_per_out_pixel
     else:
         h = hw
         for k, v in p.features:

@@ -294,6 +294,66 @@ def mobilenet_v3_small(num_classes=1000):
     return MobileNetV3("small", num_classes)
 
 
+class Fire(nn.Module):
+    """SqueezeNet's module: 1x1 squeeze-ReLU, then 1x1 and 3x3 pad-1 expands, each with ReLU, concatenated."""
+
+    def __init__(self, cin, squeeze, e1, e3):
+        super().__init__()
+        self.squeeze = nn.Conv2d(cin, squeeze, 1)
+        self.expand1x1 = nn.Conv2d(squeeze, e1, 1)
+        self.expand3x3 = nn.Conv2d(squeeze, e3, 3, padding=1)
+
+    def forward(self, x):
+        s = F.relu(self.squeeze(x))
+        return torch.cat([F.relu(self.expand1x1(s)), F.relu(self.expand3x3(s))], 1)
+
+
+def _pool_ceil():
+    return nn.MaxPool2d(3, 2, ceil_mode=True)
+
+
+class SqueezeNet(nn.Module):
+    """torchvision v0.10's squeezenet1_0 (1,248,424 parameters) / squeezenet1_1 (1,235,496): ceil-mode max
+    pools, and a head that is a 1x1 conv to the classes, ReLU and a global average pool."""
+
+    def __init__(self, version="1_0", num_classes=1000):
+        super().__init__()
+        self.version = version
+        if version == "1_0":
+            feats = [nn.Conv2d(3, 96, 7, 2), nn.ReLU(inplace=True), _pool_ceil(), Fire(96, 16, 64, 64),
+                     Fire(128, 16, 64, 64), Fire(128, 32, 128, 128), _pool_ceil(), Fire(256, 32, 128, 128),
+                     Fire(256, 48, 192, 192), Fire(384, 48, 192, 192), Fire(384, 64, 256, 256), _pool_ceil(),
+                     Fire(512, 64, 256, 256)]
+        elif version == "1_1":
+            feats = [nn.Conv2d(3, 64, 3, 2), nn.ReLU(inplace=True), _pool_ceil(), Fire(64, 16, 64, 64),
+                     Fire(128, 16, 64, 64), _pool_ceil(), Fire(128, 32, 128, 128), Fire(256, 32, 128, 128),
+                     _pool_ceil(), Fire(256, 48, 192, 192), Fire(384, 48, 192, 192), Fire(384, 64, 256, 256),
+                     Fire(512, 64, 256, 256)]
+        else:
+            raise ValueError(f"SqueezeNet version must be '1_0' or '1_1', got {version!r}")
+        self.features = nn.Sequential(*feats)
+        final = nn.Conv2d(512, num_classes, 1)
+        self.classifier = nn.Sequential(nn.Dropout(0.5), final, nn.ReLU(inplace=True), nn.AdaptiveAvgPool2d(1))
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                if m is final:
+                    nn.init.normal_(m.weight, 0.0, 0.01)
+                else:
+                    nn.init.kaiming_uniform_(m.weight)
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        return torch.flatten(self.classifier(self.features(x)), 1)
+
+
+def squeezenet1_0(num_classes=1000):
+    return SqueezeNet("1_0", num_classes)
+
+
+def squeezenet1_1(num_classes=1000):
+    return SqueezeNet("1_1", num_classes)
+
+
 def resnet18(num_classes=1000):
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes)
 
@@ -334,12 +394,13 @@ def alexnet(num_classes=1000):
     return AlexNet(num_classes)
 
 
-# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2 / V3
+# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2 / V3 + SqueezeNet
 BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet,
             "resnet101": resnet101, "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d,
             "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
             "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2,
-            "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small}
+            "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
+            "squeezenet1_0": squeezenet1_0, "squeezenet1_1": squeezenet1_1}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -400,7 +461,9 @@ ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18
            "mobilenet": "mobilenet_v2", "mobilenetv2": "mobilenet_v2", "mobilenet-v2": "mobilenet_v2",
            "mobilenetv3_large": "mobilenet_v3_large", "mobilenet-v3-large": "mobilenet_v3_large",
            "mobilenet_v3": "mobilenet_v3_large", "mobilenetv3_small": "mobilenet_v3_small",
-           "mobilenet-v3-small": "mobilenet_v3_small"}
+           "mobilenet-v3-small": "mobilenet_v3_small",
+           "squeezenet": "squeezenet1_1", "squeezenet1.1": "squeezenet1_1", "squeezenet-1.1": "squeezenet1_1",
+           "squeezenet1.0": "squeezenet1_0", "squeezenet-1.0": "squeezenet1_0"}
 
 
 def canonical(name: str) -> str:

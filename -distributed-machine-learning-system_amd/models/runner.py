@@ -243,8 +243,8 @@ class HipRunner:
 
     # -- eager forward ------------------------------------------------------
     def _guarded(self) -> bool:
-        # MobileNetV2 / V3 have no split path (their fp32 programs are true fp32), hence no range guard
-        return self.p.kind not in ("mobilenet", "mobilenet_v3") and self.p.dtype == "fp32" and self.split and self._split_ok()
+        # MobileNetV2 / V3 and SqueezeNet have no split path (their fp32 programs are true fp32), hence no range guard
+        return self.p.kind not in ("mobilenet", "mobilenet_v3", "squeezenet") and self.p.dtype == "fp32" and self.split and self._split_ok()
 
     def logits(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
                start_offset: int = 0) -> torch.Tensor:
@@ -311,6 +311,8 @@ class HipRunner:
             return self._logits_mobilenet(ims, native)
         if p.kind == "mobilenet_v3":
             return self._logits_mobilenet_v3(ims, native)
+        if p.kind == "squeezenet":
+            return self._logits_squeezenet(ims, native)
         if p.dtype == "fp32":
             return self._logits_f32(ims, native)
         s = p.stem
@@ -419,6 +421,21 @@ class HipRunner:
         h = p.fcs[0]
         x = o.conv1x1_narrow(x.view(-1, 1, 1, h.cin), h.w, h.b, h.act).view(-1, h.cout)
         return o.linear(x, p.fcs[1].w, p.fcs[1].b, relu=False, out_f32=True)
+
+    def _logits_squeezenet(self, ims: _Images, native):
+        """SqueezeNet 1.0 / 1.1 in either precision (fp32: true fp32 on the f32 MFMA): NHWC4
+        producer -> small-C stem conv with ReLU -> ceil-mode max pools and one ops.fire launch a
+        Fire module -> the head conv with its ReLU and average pool in one launch, fp32 logits.
+        Everything on the current stream."""
+        o, p, s = self.ops, self.p, self.p.stem
+        x = self._nhwc4(ims, f32=p.dtype == "fp32") if native else o.resize_crop(ims.img, 256, 224)
+        x = o.conv2d(x, s.w, s.b, s.kh, s.kw, s.stride, s.pad, True)
+        for k, v in p.features:
+            if k == "pool":
+                x = o.maxpool2d(x, *v, ceil_mode=True)
+            else:
+                x = o.fire(x, v.squeeze.w, v.squeeze.b, v.we, v.be, v.e1)
+        return o.conv1x1_relu_pool(x, p.last.w, p.last.b)
 
     def _alex_stem_fusable(self, first, feats) -> bool:
         """conv1 has the fused-stem operands and ``feats`` (what follows it)

@@ -15,7 +15,7 @@ __all__ = [
     "conv2d_wino", "wino_supported", "preprocess_pack3", "conv2d_pack3",
     "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
-    "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite",
+    "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite", "fire", "fire_ok", "conv1x1_relu_pool",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "conv3x3_split_block", "conv3x3_split_block_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -158,6 +158,28 @@ def se_excite(mean, w1, b1, w2, b2):
     Kp(C)] and ``w2`` [C, Kp(Csq)] = models.packed.pack_pw_weight, biases fp32;
     C <= 1280, Csq <= 320, multiples of 8."""
     return load().se_excite(mean, w1, b1, w2, b2)
+
+
+def fire(x, ws, bs, we, be, e1: int, out=None):
+    """SqueezeNet Fire module in ONE launch on NHWC [B, H, W, Cin], fp16 or true fp32 by ``x``'s dtype (fire.hip):
+    ``concat(relu(conv1x1(s) + b1), relu(conv3x3 pad 1(s) + b3))`` with ``s = relu(conv1x1(x, ws) + bs)``; the
+    squeeze map stays in LDS with the 3x3's zero border, the concat is written in place.  ``ws`` =
+    models.packed.pack_pw_weight ([S, Kp]), ``we`` = pack_fire_weights ([E1 + E3, Kp(9 S)]), biases fp32 (``be``:
+    b1 then b3); ``e1`` the 1x1 expand's width.  Cin % 16 == 0 up to 512, S 16 / 32 / 48 / 64, E1 and E3 % 16 == 0
+    up to 256, any H, W up to 96; anything else raises."""
+    return load().fire(x, ws, bs, we, be, int(e1), out)
+
+
+def fire_ok(h: int, w: int, cin: int, s: int, e1: int, e3: int) -> bool:
+    """Whether ``fire`` takes this shape (in both precisions)."""
+    return bool(load().fire_ok(int(h), int(w), int(cin), int(s), int(e1), int(e3)))
+
+
+def conv1x1_relu_pool(x, w, bias):
+    """``mean over pixels of relu(conv1x1(x, w) + bias)`` -> fp32 [B, N] from NHWC [B, H, W, K], fp16 or fp32
+    (fire.hip): SqueezeNet's head without its [B, H, W, N] tensor.  ``w`` = models.packed.pack_pw_weight; K, N
+    multiples of 8 up to 1280.  Fixed summation order: the same bits every run."""
+    return load().conv1x1_relu_pool(x, w, bias)
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,
@@ -419,8 +441,10 @@ def stem_fused(img_u8, w, bias, start=None, batch: int = -1, start_offset: int =
     return load().stem_fused(img_u8, w, bias, start, batch, start_offset, window, sub)
 
 
-def maxpool2d(x, k: int = 3, s: int = 2, pad: int = 1, out=None):
-    return load().maxpool2d_nhwc(x, k, s, pad, out)
+def maxpool2d(x, k: int = 3, s: int = 2, pad: int = 1, out=None, ceil_mode: bool = False):
+    """NHWC max pool, fp16 or fp32.  ``ceil_mode``: PyTorch's output size, ceil((H + 2 pad - k) / s) + 1 less one
+    where the last window would start in the right padding; windows are clipped to the input."""
+    return load().maxpool2d_nhwc(x, k, s, pad, out, bool(ceil_mode))
 
 
 def global_avgpool(x):
