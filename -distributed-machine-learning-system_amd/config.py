@@ -33,7 +33,8 @@ class ClusterConfig:
                                                       "resnext101_32x8d": 400, "wide_resnet50_2": 400,
                                                       "wide_resnet101_2": 400, "mobilenet_v2": 400,
                                                       "mobilenet_v3_large": 400, "mobilenet_v3_small": 400,
-                                                      "squeezenet1_0": 400, "squeezenet1_1": 400})
+                                                      "squeezenet1_0": 400, "squeezenet1_1": 400,
+                                                      "densenet121": 400, "densenet169": 400, "densenet201": 400})
     worker_budget: int = 8                   # reference RATE_FACTOR (:44) -> GPUs shared by jobs
     max_chunk: int = 1024                    # largest per-worker batch (HBM is not the limit)
     dataset_size: int = 10000                # reference dataset: 10,000 images (report p.1)

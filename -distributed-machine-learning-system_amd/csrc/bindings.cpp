@@ -60,6 +60,13 @@ Tensor se_excite(Tensor mean, Tensor w1, Tensor b1, Tensor w2, Tensor b2);
 Tensor fire(Tensor x, Tensor ws, Tensor bs, Tensor we, Tensor be, int64_t e1, OptTensor out);
 bool fire_ok_py(int64_t H, int64_t W, int64_t Cin, int64_t S, int64_t E1, int64_t E3);
 Tensor conv1x1_relu_pool(Tensor x, Tensor w, Tensor bias);
+// bind_dense.cpp
+Tensor dense_layer(Tensor buf, int64_t cin, Tensor scale1, Tensor shift1, Tensor w1, Tensor b1, Tensor w2);
+bool dense_layer_ok_py(int64_t H, int64_t W, int64_t cin, int64_t Ctot);
+std::vector<int64_t> dense_plan_py(int64_t H, int64_t W, int64_t cin, bool f32);
+Tensor dense_transition(Tensor x, Tensor scale, Tensor shift, Tensor w, Tensor out);
+Tensor maxpool2d_into(Tensor x, Tensor buf, int64_t k, int64_t s, int64_t pad);
+Tensor bn_relu_avgpool(Tensor buf, Tensor scale, Tensor shift);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -224,6 +231,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fire_kpad", [](int64_t S, bool f32) { return (int64_t)fire_kpad((int)S, f32); },
         "row length of fire's expand weights for S squeeze channels", py::arg("S"), py::arg("f32"));
   m.def("fire_max_w", []() { return (int64_t)fire_max_w(); }, "widest image the Fire kernel takes");
+  m.def("dense_layer", &dense_layer,
+        "DenseNet layer in one launch, in place on the block's concat buffer: channels [cin, cin + 32) from channels "
+        "[0, cin); fp16 or fp32 NHWC; the bottleneck map stays in LDS",
+        py::arg("buf"), py::arg("cin"), py::arg("scale1"), py::arg("shift1"), py::arg("w1"), py::arg("b1"),
+        py::arg("w2"));
+  m.def("dense_layer_ok", &dense_layer_ok_py, "whether the dense-layer kernel takes (H, W, cin, Ctot) in both precisions");
+  m.def("dense_plan", &dense_plan_py, "host only: (R, bands, mf, K chunk, x chunk bytes, LDS bytes) of a dense layer",
+        py::arg("H"), py::arg("W"), py::arg("cin"), py::arg("f32"));
+  m.def("dense_transition", &dense_transition,
+        "DenseNet transition in one launch: conv1x1(avgpool2x2(relu(x scale + shift))) into channels [0, C / 2) of out",
+        py::arg("buf"), py::arg("scale"), py::arg("shift"), py::arg("w"), py::arg("out"));
+  m.def("maxpool2d_into", &maxpool2d_into, "NHWC max pool into channels [0, C) of a wider buffer", py::arg("x"),
+        py::arg("buf"), py::arg("k"), py::arg("s"), py::arg("pad"));
+  m.def("bn_relu_avgpool", &bn_relu_avgpool, "mean over pixels of relu(x scale + shift) -> [B, C], bit-stable",
+        py::arg("buf"), py::arg("scale"), py::arg("shift"));
   m.def("conv1x1_relu_pool", &conv1x1_relu_pool,
         "mean over pixels of relu(1x1 conv + bias): fp32 [B, N] from fp16 or fp32 NHWC, bit-stable", py::arg("x"),
         py::arg("w"), py::arg("bias"));

@@ -337,6 +337,28 @@ int fire_max_w();
 bool conv1x1_pool_launch(const void* x, const void* w, const float* bias, float* out, int B, int HW, int K, int N,
                          bool f32, hipStream_t st);
 
+// ---- DenseNet: dense.hip ----
+// buf[B, H, W, Ctot], in place: channels [cin, cin + 32) = conv3x3 pad 1(relu(W1 relu(x scale1 + shift1) + b1)) with
+// x = channels [0, cin); buf and the weights fp16, or fp32 with f32.  w1 [128, cin] (norm2 folded in), b1 [128],
+// w2 [32, 9 * 128] tap-major, scale1 / shift1 fp32 [cin].  dense_layer_ok: cin % 32 == 0, cin + 32 <= Ctot,
+// Ctot % 8 == 0 and a band plan (dense_math.h: W <= 64).  False: unsupported shape, nothing launched.
+bool dense_layer_launch(void* buf, const float* scale1, const float* shift1, const void* w1, const float* b1,
+                        const void* w2, int B, int H, int W, int cin, int Ctot, bool f32, hipStream_t st);
+bool dense_layer_ok(int H, int W, int cin, int Ctot, bool f32);
+// the plan of a layer shape: out = {R, bands an image, mf, K chunk, x chunk bytes, LDS bytes}.  Host only.
+bool dense_plan(int H, int W, int cin, bool f32, int out[6]);
+// out[B, H / 2, W / 2, ldo], channels [0, C / 2) = W avgpool2x2(relu(x scale + shift)), x [B, H, W, C], w [C / 2, C];
+// C % 32 == 0, ldo % 8 == 0, H and W floor.  False: unsupported shape, nothing launched.
+bool dense_transition_launch(const void* x, const float* scale, const float* shift, const void* w, void* out, int B,
+                             int H, int W, int C, int ldo, bool f32, hipStream_t st);
+bool dense_transition_ok(int H, int W, int C, int ldo);
+// buf[B, Ho, Wo, ldo], channels [0, C) = max pool k / s / pad of x [B, H, W, C]; C % 8 == 0, ldo % 8 == 0, 2 pad <= k
+bool maxpool_into_launch(const void* x, void* buf, int B, int H, int W, int C, int Ho, int Wo, int ldo, int k, int s,
+                         int pad, bool f32, hipStream_t st);
+// out[B, C] (x's dtype) = mean over the HW pixels of relu(x scale + shift), fp32 sums in pixel order; C % 8 == 0
+bool bn_relu_avgpool_launch(const void* x, const float* scale, const float* shift, void* out, int B, int HW, int C,
+                            bool f32, hipStream_t st);
+
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.

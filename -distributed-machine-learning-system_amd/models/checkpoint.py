@@ -5,7 +5,9 @@ a ``state_dict`` saved from torchvision's ``alexnet`` or any member of its
 v0.10 ResNet family (``resnet18/34/50/101/152``, ``resnext50_32x4d``,
 ``resnext101_32x8d``, ``wide_resnet50_2``, ``wide_resnet101_2``; a grouped
 ``conv2.weight`` is ``[width, width // groups, 3, 3]``), its ``mobilenet_v2``, ``mobilenet_v3_large`` and ``mobilenet_v3_small``,
-its ``squeezenet1_0`` and ``squeezenet1_1`` (whose head is the conv ``classifier.1``, ``[1000, 512, 1, 1]``), or from
+its ``squeezenet1_0`` and ``squeezenet1_1`` (whose head is the conv ``classifier.1``, ``[1000, 512, 1, 1]``), its ``densenet121``, ``densenet169`` and ``densenet201`` (the key names a torchvision v0.10
+model saves: ``features.denseblock1.denselayer1.norm1.weight``, not the dotted ``norm.1`` of its oldest files;
+``densenet161`` is not served), or from
 ``reference.build``, loads strictly:
 
     state = load_state("resnet18.pth")            # or .safetensors
@@ -102,7 +104,8 @@ def model_from_state(name: str, state: dict) -> nn.Module:
     want = m.state_dict()
     want = {k: v for k, v in want.items() if not k.endswith("num_batches_tracked")}
     head = "fc" if isinstance(m, ref.ResNet) else "classifier.1" if isinstance(m, (ref.MobileNetV2, ref.SqueezeNet)) \
-        else "classifier.3" if isinstance(m, ref.MobileNetV3) else "classifier.6"
+        else "classifier.3" if isinstance(m, ref.MobileNetV3) else "classifier" if isinstance(m, ref.DenseNet) \
+        else "classifier.6"
     hw = state.get(head + ".weight")
     if hw is not None and hw.dim() == want[head + ".weight"].dim() and hw.shape[0] != NUM_CLASSES:
         raise ValueError(f"{name}: the head {head} has {hw.shape[0]} classes; only {NUM_CLASSES}-class "

@@ -21,6 +21,8 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
     excitation FCs and the classifier's first Linear are pointwise weights too
   * SqueezeNet: a Fire module's squeeze as a pointwise weight and both expands as ONE
     [E1 + E3, Kp(9 S)] tap-major weight (pack_fire_weights, fire.hip), the head conv pointwise
+  * DenseNet: a dense layer as norm1's fp32 affine, conv1 with norm2 folded in ([128, Cin]) and the 3x3 tap-major
+    ([32, 1152]) (pack_dense_layer, dense.hip); a transition as its norm's affine and a [C / 2, C] weight
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -139,9 +141,46 @@ class Fire:
 
 
 @dataclass
+class DenseLayer:
+    """DenseNet layer for ops.dense_layer (pack_dense_layer): ``scale1`` / ``shift1`` norm1 as an fp32 affine on the
+    layer's ``cin`` input channels, ``w1`` [128, cin] conv1 with norm2 folded in and ``b1`` norm2's shift, ``w2``
+    [32, 1152] the 3x3 tap-major."""
+    scale1: torch.Tensor
+    shift1: torch.Tensor
+    w1: torch.Tensor
+    b1: torch.Tensor
+    w2: torch.Tensor
+    cin: int
+
+    def to(self, device):
+        return replace(self, **{f.name: getattr(self, f.name).to(device) for f in fields(self) if f.name != "cin"})
+
+    @property
+    def flops_per_out_pixel(self) -> int:
+        return 2 * (self.cin * DENSE_M + 9 * DENSE_M * DENSE_G)
+
+
+@dataclass
+class DenseTransition:
+    """DenseNet transition for ops.dense_transition: norm as an fp32 affine on ``cin`` channels, ``w`` [cin / 2, cin]."""
+    scale: torch.Tensor
+    shift: torch.Tensor
+    w: torch.Tensor
+    cin: int
+
+    def to(self, device):
+        return replace(self, scale=self.scale.to(device), shift=self.shift.to(device), w=self.w.to(device))
+
+    @property
+    def flops_per_out_pixel(self) -> int:
+        """Per INPUT pixel: the module convolves before it pools."""
+        return 2 * self.cin * (self.cin // 2)
+
+
+@dataclass
 class Program:
     name: str
-    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3" | "squeezenet"
+    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3" | "squeezenet" | "densenet"
     stem: Conv | None = None  # resnet
     blocks: list = field(default_factory=list)
     features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p)); squeezenet, between
@@ -151,9 +190,13 @@ class Program:
     fcs: list = field(default_factory=list)       # list[Conv] as 1x1 convs (last -> fp32 logits)
     num_classes: int = 1000
     dtype: str = "fp16"       # activation / weight precision: "fp16" | "fp32" (reference precision)
+    # densenet: ``features`` between ``stem`` and ``head_norm`` is ("dense", DenseLayer) | ("transition",
+    # DenseTransition) in module order; ``head_norm`` = norm5 as fp32 (scale, shift) for ops.bn_relu_avgpool
+    head_norm: tuple | None = None
 
     def to(self, device):
         return replace(self, stem=self.stem.to(device) if self.stem else None,
+                       head_norm=tuple(t.to(device) for t in self.head_norm) if self.head_norm else None,
                        blocks=[b.to(device) for b in self.blocks],
                        features=[(k, v if k == "pool" else v.to(device)) for k, v in self.features],
                        mblocks=[b.to(device) for b in self.mblocks], last=self.last.to(device) if self.last else None,
@@ -166,6 +209,10 @@ class Program:
         for k, v in self.features:
             if k == "fire":                   # the expands as stored: the 1x1's rows are as long as the 3x3's
                 tot += v.we.numel() * v.we.element_size() + v.be.numel() * 4
+            elif k in ("dense", "transition"):    # packed tensors, not Convs: the weights and the fp32 affines
+                tot += sum(t.numel() * t.element_size() for t in vars(v).values() if isinstance(t, torch.Tensor))
+        for t in self.head_norm or ():
+            tot += t.numel() * 4
         return tot
 
     def all_convs(self):
@@ -669,6 +716,52 @@ def make_fire(f: "ref.Fire", dtype: str = "fp16") -> Fire:
     return Fire(make_pw(f.squeeze, None, 1, dtype), we, be, f.expand1x1.out_channels, f.expand3x3.out_channels)
 
 
+# ---------------------------------------------------------------------------
+# DenseNet layers and transitions (dense.hip)
+# ---------------------------------------------------------------------------
+
+DENSE_M, DENSE_G = 128, 32        # bottleneck width and growth the kernel is compiled for
+
+
+def bn_affine_f64(bn: nn.BatchNorm2d) -> tuple[torch.Tensor, torch.Tensor]:
+    """An eval-mode BatchNorm as y = x scale + shift, in fp64."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    return scale, bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+
+
+def pack_dense_layer(layer: "ref.DenseLayer", dtype: str = "fp16") -> DenseLayer:
+    """norm1 stays an fp32 affine (it sits in front of conv1, on a tensor every later layer reads through its own
+    norm1: it folds into no weight); norm2 folds into conv1 in fp64 (``fold_bn_f64``); conv2 [32, 128, 3, 3] ->
+    [32, 1152] tap-major, k = (3 kh + kw) 128 + c."""
+    c1, c2 = layer.conv1, layer.conv2
+    if tuple(c1.weight.shape[:1] + c1.weight.shape[2:]) != (DENSE_M, 1, 1) or tuple(c2.weight.shape) != \
+            (DENSE_G, DENSE_M, 3, 3) or c1.in_channels % 32 or c1.bias is not None or c2.bias is not None:
+        raise ValueError(f"dense layers are 1x1 Cin->{DENSE_M} (Cin % 32 == 0) then 3x3 {DENSE_M}->{DENSE_G}, bias-free, "
+                         f"got {tuple(c1.weight.shape)}, {tuple(c2.weight.shape)}")
+    scale1, shift1 = bn_affine_f64(layer.norm1)
+    w1, b1 = fold_bn_f64(c1.weight, None, layer.norm2)
+    dt = _dt(dtype)
+    return DenseLayer(scale1.float().contiguous(), shift1.float().contiguous(),
+                      w1.reshape(DENSE_M, -1).to(dt).contiguous(), b1.float().contiguous(),
+                      c2.weight.detach().permute(0, 2, 3, 1).reshape(DENSE_G, 9 * DENSE_M).to(dt).contiguous(),
+                      c1.in_channels)
+
+
+def unpack_dense_layer(d: DenseLayer) -> tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of pack_dense_layer's weight layouts -> fp32 ([128, cin, 1, 1] with norm2 folded in, [32, 128, 3, 3])."""
+    w1 = d.w1.float().reshape(DENSE_M, d.cin, 1, 1).contiguous()
+    return w1, d.w2.float().reshape(DENSE_G, 3, 3, DENSE_M).permute(0, 3, 1, 2).contiguous()
+
+
+def pack_dense_transition(t: nn.Sequential, dtype: str = "fp16") -> DenseTransition:
+    c = t.conv.in_channels
+    if tuple(t.conv.weight.shape) != (c // 2, c, 1, 1) or c % 32 or t.conv.bias is not None:
+        raise ValueError(f"transitions are bias-free 1x1 convs C -> C / 2 with C % 32 == 0, got {tuple(t.conv.weight.shape)}")
+    scale, shift = bn_affine_f64(t.norm)
+    return DenseTransition(scale.float().contiguous(), shift.float().contiguous(),
+                           t.conv.weight.detach().reshape(c // 2, c).to(_dt(dtype)).contiguous(), c)
+
+
 # Winograd F(2x2, 3x3) filter transform (Lavin & Gray): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
@@ -832,6 +925,21 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
         p.last = make_pw(m.classifier[1], None, 1, dt)      # the head: ops.conv1x1_relu_pool -> fp32 logits
         p.num_classes = m.classifier[1].out_channels
         return p
+    if isinstance(m, ref.DenseNet):
+        f = m.features
+        if m.growth != DENSE_G or f.conv0.out_channels != 64:
+            raise ValueError(f"DenseNets are served at growth {DENSE_G} with a 64-channel stem (not densenet161)")
+        p = Program(name, "densenet", stem=make_conv(f.conv0, f.norm0, True, dt), dtype=dt)
+        for key, mod in f.named_children():
+            if key.startswith("denseblock"):
+                p.features += [("dense", pack_dense_layer(layer, dt)) for layer in mod.children()]
+            elif key.startswith("transition"):
+                p.features.append(("transition", pack_dense_transition(mod, dt)))
+        p.head_norm = tuple(t.float().contiguous() for t in bn_affine_f64(f.norm5))
+        p.fcs = [make_fc(m.classifier, False, dtype=dt)]
+        p.fcs[0].sw = None              # true fp32: no split path
+        p.num_classes = m.classifier.out_features
+        return p
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
@@ -903,6 +1011,18 @@ def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
         for k, v in p.features:
             x = _emu_fire(v, x) if k == "fire" else F.max_pool2d(x, *v, ceil_mode=True)
         x = _emu_conv(p.last, x).mean(dim=(2, 3))
+    elif p.kind == "densenet":
+        aff = lambda t, s, b: t * s.to(t.device).view(1, -1, 1, 1) + b.to(t.device).view(1, -1, 1, 1)
+        x = F.max_pool2d(_emu_conv(p.stem, x), 3, 2, 1)
+        for k, v in p.features:                    # module order: the transition convolves, then pools
+            if k == "dense":
+                w1, w2 = unpack_dense_layer(v)
+                t = F.relu(F.conv2d(F.relu(aff(x, v.scale1, v.shift1)), w1.to(x.device), v.b1.to(x.device)))
+                x = torch.cat([x, F.conv2d(t, w2.to(x.device), padding=1)], 1)
+            else:
+                w = v.w.float().reshape(v.cin // 2, v.cin, 1, 1).to(x.device)
+                x = F.avg_pool2d(F.conv2d(F.relu(aff(x, v.scale, v.shift)), w), 2, 2)
+        x = F.relu(aff(x, *p.head_norm)).mean(dim=(2, 3))
     else:
         for k, v in p.features:
             x = _emu_conv(v, x) if k == "conv" else F.max_pool2d(x, *v)
@@ -949,6 +1069,14 @@ def program_flops(p: Program, hw: int = 224) -> float:
             else:
                 h = -(-(h + 2 * v[2] - v[0]) // v[1]) + 1      # ceil mode (no window starts in the padding: pad 0)
         tot += h * h * p.last.flops_per_out_pixel
+    elif p.kind == "densenet":
+        h = out_hw(hw, p.stem)
+        tot += h * h * p.stem.flops_per_out_pixel
+        h = (h + 2 - 3) // 2 + 1
+        for k, v in p.features:                    # the module's MACs: the transition conv at the unpooled size
+            tot += h * h * v.flops_per_out_pixel
+            if k == "transition":
+                h //= 2
     else:
         h = hw
         for k, v in p.features:

@@ -354,6 +354,88 @@ def squeezenet1_1(num_classes=1000):
     return SqueezeNet("1_1", num_classes)
 
 
+class DenseLayer(nn.Module):
+    """torchvision's ``_DenseLayer``: BN -> ReLU -> 1x1 to 4 * growth -> BN -> ReLU -> 3x3 to growth."""
+
+    def __init__(self, cin, growth, bn_size=4):
+        super().__init__()
+        self.norm1 = nn.BatchNorm2d(cin)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.conv1 = _conv(cin, bn_size * growth, 1)
+        self.norm2 = nn.BatchNorm2d(bn_size * growth)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.conv2 = _conv(bn_size * growth, growth, 3, 1, 1)
+
+    def forward(self, x):
+        return self.conv2(self.relu2(self.norm2(self.conv1(self.relu1(self.norm1(x))))))
+
+
+class DenseBlock(nn.Module):
+    """``denselayer{j}`` children, each fed the concatenation of the block's input and every earlier layer's output."""
+
+    def __init__(self, n, cin, growth):
+        super().__init__()
+        for j in range(n):
+            self.add_module(f"denselayer{j + 1}", DenseLayer(cin + j * growth, growth))
+
+    def forward(self, x):
+        for layer in self.children():
+            x = torch.cat([x, layer(x)], 1)
+        return x
+
+
+class DenseNet(nn.Module):
+    """torchvision v0.10 DenseNet-BC (growth 32, bn_size 4, 64 stem channels, compression 0.5), its key names."""
+
+    def __init__(self, block_config, growth=32, num_init=64, num_classes=1000):
+        super().__init__()
+        self.growth, self.block_config = growth, tuple(block_config)
+        f = nn.Sequential()
+        f.add_module("conv0", _conv(3, num_init, 7, 2, 3))
+        f.add_module("norm0", nn.BatchNorm2d(num_init))
+        f.add_module("relu0", nn.ReLU(inplace=True))
+        f.add_module("pool0", nn.MaxPool2d(3, 2, 1))
+        c = num_init
+        for i, n in enumerate(block_config):
+            f.add_module(f"denseblock{i + 1}", DenseBlock(n, c, growth))
+            c += n * growth
+            if i != len(block_config) - 1:
+                t = nn.Sequential()
+                t.add_module("norm", nn.BatchNorm2d(c))
+                t.add_module("relu", nn.ReLU(inplace=True))
+                t.add_module("conv", _conv(c, c // 2, 1))
+                t.add_module("pool", nn.AvgPool2d(2, 2))
+                f.add_module(f"transition{i + 1}", t)
+                c //= 2
+        f.add_module("norm5", nn.BatchNorm2d(c))
+        self.features = f
+        self.classifier = nn.Linear(c, num_classes)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.ones_(m.weight)
+                nn.init.zeros_(m.bias)
+            elif isinstance(m, nn.Linear):
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        x = F.relu(self.features(x))
+        return self.classifier(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
+
+
+def densenet121(num_classes=1000):
+    return DenseNet((6, 12, 24, 16), num_classes=num_classes)
+
+
+def densenet169(num_classes=1000):
+    return DenseNet((6, 12, 32, 32), num_classes=num_classes)
+
+
+def densenet201(num_classes=1000):
+    return DenseNet((6, 12, 48, 32), num_classes=num_classes)
+
+
 def resnet18(num_classes=1000):
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes)
 
@@ -400,7 +482,8 @@ BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "a
             "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
             "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2,
             "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
-            "squeezenet1_0": squeezenet1_0, "squeezenet1_1": squeezenet1_1}
+            "squeezenet1_0": squeezenet1_0, "squeezenet1_1": squeezenet1_1,
+            "densenet121": densenet121, "densenet169": densenet169, "densenet201": densenet201}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -463,7 +546,9 @@ ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18
            "mobilenet_v3": "mobilenet_v3_large", "mobilenetv3_small": "mobilenet_v3_small",
            "mobilenet-v3-small": "mobilenet_v3_small",
            "squeezenet": "squeezenet1_1", "squeezenet1.1": "squeezenet1_1", "squeezenet-1.1": "squeezenet1_1",
-           "squeezenet1.0": "squeezenet1_0", "squeezenet-1.0": "squeezenet1_0"}
+           "squeezenet1.0": "squeezenet1_0", "squeezenet-1.0": "squeezenet1_0",
+           "densenet": "densenet121", "densenet-121": "densenet121", "densenet-169": "densenet169",
+           "densenet-201": "densenet201"}
 
 
 def canonical(name: str) -> str:

@@ -243,8 +243,10 @@ class HipRunner:
 
     # -- eager forward ------------------------------------------------------
     def _guarded(self) -> bool:
-        # MobileNetV2 / V3 and SqueezeNet have no split path (their fp32 programs are true fp32), hence no range guard
-        return self.p.kind not in ("mobilenet", "mobilenet_v3", "squeezenet") and self.p.dtype == "fp32" and self.split and self._split_ok()
+        # MobileNetV2 / V3, SqueezeNet and DenseNet have no split path (their fp32 programs are true fp32), hence no
+        # range guard
+        return self.p.kind not in ("mobilenet", "mobilenet_v3", "squeezenet", "densenet") and self.p.dtype == "fp32" \
+            and self.split and self._split_ok()
 
     def logits(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
                start_offset: int = 0) -> torch.Tensor:
@@ -313,6 +315,8 @@ class HipRunner:
             return self._logits_mobilenet_v3(ims, native)
         if p.kind == "squeezenet":
             return self._logits_squeezenet(ims, native)
+        if p.kind == "densenet":
+            return self._logits_densenet(ims, native)
         if p.dtype == "fp32":
             return self._logits_f32(ims, native)
         s = p.stem
@@ -436,6 +440,35 @@ class HipRunner:
             else:
                 x = o.fire(x, v.squeeze.w, v.squeeze.b, v.we, v.be, v.e1)
         return o.conv1x1_relu_pool(x, p.last.w, p.last.b)
+
+    def _logits_densenet(self, ims: _Images, native):
+        """DenseNet-121 / 169 / 201 in either precision (fp32: true fp32 on the f32 MFMA): NHWC4 producer ->
+        small-C stem conv with ReLU -> max pool straight into block 1's buffer -> per block ONE buffer of the
+        block's final width and one ops.dense_layer launch a layer (each appends its 32 channels in place) ->
+        ops.dense_transition into the next block's buffer -> norm5 + ReLU + average pool -> FC.  Buffers are
+        allocated per call on the current stream, like every other activation."""
+        o, p, s = self.ops, self.p, self.p.stem
+        x = self._nhwc4(ims, f32=p.dtype == "fp32") if native else o.resize_crop(ims.img, 256, 224)
+        x = o.conv2d(x, s.w, s.b, s.kh, s.kw, s.stride, s.pad, True)
+        feats, i, buf = p.features, 0, None
+        while i < len(feats):
+            n = 0
+            while i + n < len(feats) and feats[i + n][0] == "dense":
+                n += 1
+            c0 = feats[i][1].cin
+            if buf is None:
+                shape = (x.shape[0], (x.shape[1] - 1) // 2 + 1, (x.shape[2] - 1) // 2 + 1, c0 + 32 * n)
+                buf = o.maxpool2d_into(x, torch.empty(shape, dtype=x.dtype, device=x.device), 3, 2, 1)
+            else:
+                t = feats[i - 1][1]
+                nxt = torch.empty((buf.shape[0], buf.shape[1] // 2, buf.shape[2] // 2, c0 + 32 * n), dtype=buf.dtype,
+                                  device=buf.device)
+                buf = o.dense_transition(buf, t.scale, t.shift, t.w, nxt)
+            for _, d in feats[i:i + n]:
+                o.dense_layer(buf, d.cin, d.scale1, d.shift1, d.w1, d.b1, d.w2)
+            i += n + 1
+        x = o.bn_relu_avgpool(buf, *p.head_norm)
+        return o.linear(x, p.fcs[0].w, p.fcs[0].b, relu=False, out_f32=True)
 
     def _alex_stem_fusable(self, first, feats) -> bool:
         """conv1 has the fused-stem operands and ``feats`` (what follows it)

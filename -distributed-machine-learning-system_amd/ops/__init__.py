@@ -16,6 +16,7 @@ __all__ = [
     "float_to_nhwc4", "float_to_pack3", "float_to_pack3_split",
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
     "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite", "fire", "fire_ok", "conv1x1_relu_pool",
+    "dense_layer", "dense_layer_ok", "dense_plan", "dense_transition", "maxpool2d_into", "bn_relu_avgpool",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "conv3x3_split_block", "conv3x3_split_block_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -180,6 +181,45 @@ def conv1x1_relu_pool(x, w, bias):
     (fire.hip): SqueezeNet's head without its [B, H, W, N] tensor.  ``w`` = models.packed.pack_pw_weight; K, N
     multiples of 8 up to 1280.  Fixed summation order: the same bits every run."""
     return load().conv1x1_relu_pool(x, w, bias)
+
+
+def dense_layer(buf, cin: int, scale1, shift1, w1, b1, w2):
+    """DenseNet layer in ONE launch, in place on the block's concat buffer ``buf`` [B, H, W, Ctot], fp16 or true fp32 by
+    its dtype (dense.hip): channels [cin, cin + 32) = ``conv3x3 pad 1(relu(conv1x1(relu(x scale1 + shift1), w1) + b1), w2)``
+    with x = channels [0, cin); nothing else is touched, ``buf`` is returned.  ``scale1`` / ``shift1`` fp32 [cin]
+    (norm1), ``w1`` [128, cin] (conv1 with norm2 folded in), ``b1`` fp32 [128], ``w2`` [32, 1152] tap-major
+    (models.packed.pack_dense_layer).  cin % 32 == 0, cin + 32 <= Ctot, Ctot % 8 == 0, W <= 64; anything else raises."""
+    return load().dense_layer(buf, int(cin), scale1, shift1, w1, b1, w2)
+
+
+def dense_layer_ok(h: int, w: int, cin: int, ctot: int) -> bool:
+    """Whether ``dense_layer`` takes this shape (in both precisions)."""
+    return bool(load().dense_layer_ok(int(h), int(w), int(cin), int(ctot)))
+
+
+def dense_plan(h: int, w: int, cin: int, f32: bool = False) -> dict:
+    """The band plan ``dense_layer`` launches with (csrc/dense_math.h): rows a band, bands an image, pixel chunk
+    (16 mf), K chunk, and LDS bytes.  Host only, needs no GPU."""
+    r, nbands, mf, kc, xbytes, lds = (int(v) for v in load().dense_plan(int(h), int(w), int(cin), bool(f32)))
+    return {"R": r, "bands": nbands, "mf": mf, "kc": kc, "xbytes": xbytes, "lds": lds}
+
+
+def dense_transition(buf, scale, shift, w, out):
+    """DenseNet transition in ONE launch (dense.hip): ``conv1x1(avgpool2x2(relu(buf scale + shift)), w)`` -- the pool
+    first, it commutes with the bias-free conv -- into channels [0, C / 2) of ``out`` [B, H // 2, W // 2, Cnext] (the
+    next block's buffer; its other channels are untouched).  ``buf`` [B, H, W, C], C % 32 == 0; ``w`` [C / 2, C]."""
+    return load().dense_transition(buf, scale, shift, w, out)
+
+
+def maxpool2d_into(x, buf, k: int = 3, s: int = 2, pad: int = 1):
+    """NHWC max pool of ``x`` [B, H, W, C] into channels [0, C) of the wider ``buf`` [B, Ho, Wo, Ctot]."""
+    return load().maxpool2d_into(x, buf, int(k), int(s), int(pad))
+
+
+def bn_relu_avgpool(buf, scale, shift):
+    """``mean over pixels of relu(buf scale + shift)`` -> [B, C] in ``buf``'s dtype: DenseNet's norm5 + ReLU + global
+    average pool; fp32 sums in a fixed order, the same bits every run."""
+    return load().bn_relu_avgpool(buf, scale, shift)
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,
