@@ -34,7 +34,9 @@ class ClusterConfig:
                                                       "wide_resnet101_2": 400, "mobilenet_v2": 400,
                                                       "mobilenet_v3_large": 400, "mobilenet_v3_small": 400,
                                                       "squeezenet1_0": 400, "squeezenet1_1": 400,
-                                                      "densenet121": 400, "densenet169": 400, "densenet201": 400})
+                                                      "densenet121": 400, "densenet169": 400, "densenet201": 400,
+                                                      "shufflenet_v2_x0_5": 400, "shufflenet_v2_x1_0": 400,
+                                                      "shufflenet_v2_x1_5": 400})
     worker_budget: int = 8                   # reference RATE_FACTOR (:44) -> GPUs shared by jobs
     max_chunk: int = 1024                    # largest per-worker batch (HBM is not the limit)
     dataset_size: int = 10000                # reference dataset: 10,000 images (report p.1)

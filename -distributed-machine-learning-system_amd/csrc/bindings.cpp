@@ -67,6 +67,11 @@ std::vector<int64_t> dense_plan_py(int64_t H, int64_t W, int64_t cin, bool f32);
 Tensor dense_transition(Tensor x, Tensor scale, Tensor shift, Tensor w, Tensor out);
 Tensor maxpool2d_into(Tensor x, Tensor buf, int64_t k, int64_t s, int64_t pad);
 Tensor bn_relu_avgpool(Tensor buf, Tensor scale, Tensor shift);
+// bind_shuffle.cpp
+Tensor shuffle_unit(Tensor x, Tensor w1, Tensor b1, Tensor wd, Tensor bd, Tensor w2, Tensor b2, int64_t stride,
+                    OptTensor wd1, OptTensor bd1, OptTensor wp1, OptTensor bp1, int64_t c, OptTensor out);
+std::vector<int64_t> shuffle_plan_py(int64_t H, int64_t W, int64_t cin, int64_t c, int64_t stride, bool f32);
+bool shuffle_unit_ok_py(int64_t H, int64_t W, int64_t cin, int64_t c, int64_t stride);
 // bind_conv_f32.cpp
 Tensor conv2d_nhwc_f32(Tensor x, Tensor w, Tensor bias, OptTensor res, int64_t KH, int64_t KW, int64_t stride,
                        int64_t pad, bool relu, int64_t tile, OptTensor out);
@@ -246,6 +251,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("buf"), py::arg("k"), py::arg("s"), py::arg("pad"));
   m.def("bn_relu_avgpool", &bn_relu_avgpool, "mean over pixels of relu(x scale + shift) -> [B, C], bit-stable",
         py::arg("buf"), py::arg("scale"), py::arg("shift"));
+  m.def("shuffle_unit", &shuffle_unit,
+        "ShuffleNetV2 unit in one launch: channel split, 1x1, depthwise 3x3, 1x1, concat and channel shuffle; fp16 or "
+        "fp32 NHWC, stride 1 or 2 (stride 2 with branch 1's operands); c < 0: the input's width",
+        py::arg("x"), py::arg("w1"), py::arg("b1"), py::arg("wd"), py::arg("bd"), py::arg("w2"), py::arg("b2"),
+        py::arg("stride") = 1, py::arg("wd1") = py::none(), py::arg("bd1") = py::none(), py::arg("wp1") = py::none(),
+        py::arg("bp1") = py::none(), py::arg("c") = -1, py::arg("out") = py::none());
+  m.def("shuffle_plan", &shuffle_plan_py,
+        "host only: (R, bands, images a workgroup, LDS bytes, hp, Kx, Cp, Cpin) of a ShuffleNetV2 unit", py::arg("H"),
+        py::arg("W"), py::arg("cin"), py::arg("c"), py::arg("stride"), py::arg("f32"));
+  m.def("shuffle_unit_ok", &shuffle_unit_ok_py, "whether the fused unit takes (H, W, cin, c, stride) in both precisions");
   m.def("conv1x1_relu_pool", &conv1x1_relu_pool,
         "mean over pixels of relu(1x1 conv + bias): fp32 [B, N] from fp16 or fp32 NHWC, bit-stable", py::arg("x"),
         py::arg("w"), py::arg("bias"));

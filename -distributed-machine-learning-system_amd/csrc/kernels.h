@@ -359,6 +359,27 @@ bool maxpool_into_launch(const void* x, void* buf, int B, int H, int W, int C, i
 bool bn_relu_avgpool_launch(const void* x, const float* scale, const float* shift, void* out, int B, int HW, int C,
                             bool f32, hipStream_t st);
 
+// ---- ShuffleNetV2: shuffle_unit.hip ----
+// A whole unit in one launch, x [B, H, W, Cpin] -> out [B, Ho, Wo, Cp], fp16 or fp32 with f32; Cp = roundup(c, 8), the
+// other widths (hp, Kx) as shuffle_math.h derives them from (cin, c, stride).
+//   stride 1: out[2i] = x[i], out[2i + 1] = relu(w2 dw(relu(w1 x[h:c] + b1)) + b2)[i]       (h = c / 2, cin == c)
+//   stride 2: out[2i] = relu(wp1 dw1(x) + bp1)[i], out[2i + 1] as above with w1 over every input channel
+// w1, wp1 [hp, Kx], w2 [hp, hp], wd [9, hp], wd1 [9, Kx] in x's dtype; b1, bd, b2, bp1 [hp], bd1 [Kx] fp32.  Rows and
+// columns outside the logical widths are zero.  Pad channels [c, Cp) are written as zero.  False: unsupported shape
+// or no band plan, nothing launched.
+struct ShuffleUnitWeights {
+  const void* w1; const float* b1;
+  const void* wd; const float* bd;
+  const void* w2; const float* b2;
+  const void* wd1; const float* bd1;      // stride 2 only
+  const void* wp1; const float* bp1;
+};
+bool shuffle_unit_launch(const void* x, void* out, const ShuffleUnitWeights& w, int B, int H, int W, int cin, int c,
+                         int stride, bool f32, hipStream_t st);
+// the plan of a unit shape: out = {R, bands an image, images a workgroup, LDS bytes, hp, Kx, Cp, Cpin, LDS bytes of the
+// whole image as one band}.  Host only.
+bool shuffle_plan(int H, int W, int cin, int c, int stride, bool f32, int out[9]);
+
 // ---- JPEG decode (jpeg_decode.hip): one batch of images of different sizes ----
 // One descriptor per image on the device; the host (bind_jpeg.cpp jpeg_plan) has
 // checked every offset and extent in it against the buffers the kernels get.

@@ -150,7 +150,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("model", help="alexnet | resnet18 | resnet | resnet34 | resnet50 | resnet101 | resnet152 | resnext50_32x4d | "
                                   "resnext101_32x8d | wide_resnet50_2 | wide_resnet101_2 | mobilenet_v2 | "
                                   "mobilenet_v3_large | mobilenet_v3_small | squeezenet1_0 | squeezenet1_1 | "
-                                  "densenet121 | densenet169 | densenet201")
+                                  "densenet121 | densenet169 | densenet201 | shufflenet_v2_x0_5 | shufflenet_v2_x1_0 | "
+                                  "shufflenet_v2_x1_5")
     ap.add_argument("start", type=int)
     ap.add_argument("end", type=int)
     ap.add_argument("--dir", default=None, help="image directory (default: ./<model>, else synthetic)")

@@ -7,7 +7,8 @@ v0.10 ResNet family (``resnet18/34/50/101/152``, ``resnext50_32x4d``,
 ``conv2.weight`` is ``[width, width // groups, 3, 3]``), its ``mobilenet_v2``, ``mobilenet_v3_large`` and ``mobilenet_v3_small``,
 its ``squeezenet1_0`` and ``squeezenet1_1`` (whose head is the conv ``classifier.1``, ``[1000, 512, 1, 1]``), its ``densenet121``, ``densenet169`` and ``densenet201`` (the key names a torchvision v0.10
 model saves: ``features.denseblock1.denselayer1.norm1.weight``, not the dotted ``norm.1`` of its oldest files;
-``densenet161`` is not served), or from
+``densenet161`` is not served), its ``shufflenet_v2_x0_5``, ``shufflenet_v2_x1_0`` and ``shufflenet_v2_x1_5`` (head
+``fc``, ``[1000, 1024]``; ``shufflenet_v2_x2_0`` is not served), or from
 ``reference.build``, loads strictly:
 
     state = load_state("resnet18.pth")            # or .safetensors
@@ -103,7 +104,7 @@ def model_from_state(name: str, state: dict) -> nn.Module:
     m = ref.BUILDERS[name]()
     want = m.state_dict()
     want = {k: v for k, v in want.items() if not k.endswith("num_batches_tracked")}
-    head = "fc" if isinstance(m, ref.ResNet) else "classifier.1" if isinstance(m, (ref.MobileNetV2, ref.SqueezeNet)) \
+    head = "fc" if isinstance(m, (ref.ResNet, ref.ShuffleNetV2)) else "classifier.1" if isinstance(m, (ref.MobileNetV2, ref.SqueezeNet)) \
         else "classifier.3" if isinstance(m, ref.MobileNetV3) else "classifier" if isinstance(m, ref.DenseNet) \
         else "classifier.6"
     hw = state.get(head + ".weight")

@@ -23,6 +23,8 @@ of ops whose weights are laid out for the gfx950 implicit-GEMM kernel:
     [E1 + E3, Kp(9 S)] tap-major weight (pack_fire_weights, fire.hip), the head conv pointwise
   * DenseNet: a dense layer as norm1's fp32 affine, conv1 with norm2 folded in ([128, Cin]) and the 3x3 tap-major
     ([32, 1152]) (pack_dense_layer, dense.hip); a transition as its norm's affine and a [C / 2, C] weight
+  * ShuffleNetV2: a unit as zero-padded row-major 1x1 weights and tap-major depthwise weights
+    (pack_shuffle_unit, shuffle_unit.hip); width 116 is stored as 120 channels, the pad rows of every weight zero
   * AlexNet fc6 columns permuted from NCHW-flatten to NHWC-flatten order
   * dropout elided (identity in eval), AdaptiveAvgPool(6,6) elided at 224 input
 
@@ -178,9 +180,41 @@ class DenseTransition:
 
 
 @dataclass
+class ShuffleUnit:
+    """ShuffleNetV2 unit for ops.shuffle_unit (pack_shuffle_unit): branch 2 as ``w1`` [hp, Kx], ``wd`` [9, hp], ``w2``
+    [hp, hp] with fp32 biases ``b1`` / ``bd`` / ``b2`` [hp]; at stride 2 branch 1 as ``wd1`` [9, Kx], ``bd1`` [Kx],
+    ``wp1`` [hp, Kx], ``bp1`` [hp].  ``cin`` / ``c``: logical input and output widths."""
+    w1: torch.Tensor
+    b1: torch.Tensor
+    wd: torch.Tensor
+    bd: torch.Tensor
+    w2: torch.Tensor
+    b2: torch.Tensor
+    cin: int
+    c: int
+    stride: int = 1
+    wd1: torch.Tensor | None = None
+    bd1: torch.Tensor | None = None
+    wp1: torch.Tensor | None = None
+    bp1: torch.Tensor | None = None
+
+    def to(self, device):
+        vals = {f.name: getattr(self, f.name) for f in fields(self)}
+        return replace(self, **{k: v.to(device) for k, v in vals.items() if isinstance(v, torch.Tensor)})
+
+    def flops(self, hin: int) -> tuple[int, int]:
+        """(FLOPs an image, output size) at input size ``hin``: pw1 runs at the input size, the rest at the output's."""
+        h, ho = self.c // 2, hin if self.stride == 1 else (hin - 1) // 2 + 1
+        if self.stride == 1:
+            return 2 * ho * ho * (2 * h * h + 9 * h), ho
+        return 2 * (hin * hin * self.cin * h + ho * ho * (9 * h + h * h + 9 * self.cin + self.cin * h)), ho
+
+
+@dataclass
 class Program:
     name: str
-    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3" | "squeezenet" | "densenet"
+    kind: str                 # "resnet" | "alexnet" | "mobilenet" (V2) | "mobilenet_v3" | "squeezenet" | "densenet" |
+    #                           "shufflenet": ``features`` = ("shuffle", ShuffleUnit) between ``stem`` + pool and ``last``
     stem: Conv | None = None  # resnet
     blocks: list = field(default_factory=list)
     features: list = field(default_factory=list)  # alexnet: ("conv", Conv) | ("pool", (k, s, p)); squeezenet, between
@@ -209,7 +243,7 @@ class Program:
         for k, v in self.features:
             if k == "fire":                   # the expands as stored: the 1x1's rows are as long as the 3x3's
                 tot += v.we.numel() * v.we.element_size() + v.be.numel() * 4
-            elif k in ("dense", "transition"):    # packed tensors, not Convs: the weights and the fp32 affines
+            elif k in ("dense", "transition", "shuffle"):    # packed tensors, not Convs: the weights and the fp32 affines
                 tot += sum(t.numel() * t.element_size() for t in vars(v).values() if isinstance(t, torch.Tensor))
         for t in self.head_norm or ():
             tot += t.numel() * 4
@@ -762,6 +796,65 @@ def pack_dense_transition(t: nn.Sequential, dtype: str = "fp16") -> DenseTransit
                            t.conv.weight.detach().reshape(c // 2, c).to(_dt(dtype)).contiguous(), c)
 
 
+# ---------------------------------------------------------------------------
+# ShuffleNetV2 units (shuffle_unit.hip)
+# ---------------------------------------------------------------------------
+
+def shuffle_dims(cin: int, c: int, stride: int, dtype: str = "fp16") -> tuple[int, int, int]:
+    """(hp, k0, Kx) of csrc/shuffle_math.h: the branch width padded to the MFMA K step, the first input channel pw1
+    walks (stride 1: floor8(h)) and pw1's K."""
+    ks, h = (16 if dtype == "fp32" else 32), c // 2
+    cpin = -(-(c if stride == 1 else cin) // 8) * 8
+    k0 = h // 8 * 8 if stride == 1 else 0
+    return -(-h // ks) * ks, k0, -(-(cpin - k0) // ks) * ks
+
+
+def _padded(t: torch.Tensor, shape, at, dt) -> torch.Tensor:
+    """``t`` at offset ``at`` of a zero tensor of ``shape``."""
+    p = torch.zeros(shape, dtype=dt)
+    p[tuple(slice(o, o + n) for o, n in zip(at, t.shape))] = t.to(dt)
+    return p
+
+
+def pack_shuffle_unit(u: "ref.ShuffleUnit", dtype: str = "fp16") -> ShuffleUnit:
+    """BN folds into every conv in fp64.  1x1 weights are row-major with zero rows from h and zero columns outside the
+    channels the conv reads: at stride 1 column j is input channel k0 + j, so columns below h - k0 (the x1 half) and
+    from c - k0 (the pad of width 116) are zero.  Depthwise weights are tap-major [9, C]."""
+    b2 = u.branch2
+    cin, h, stride = (b2[0].in_channels if u.stride == 2 else 2 * b2[0].in_channels), b2[0].out_channels, u.stride
+    c, dt = 2 * h, _dt(dtype)
+    hp, k0, kx = shuffle_dims(cin, c, stride, dtype)
+    col = h - k0 if stride == 1 else 0
+    w1, b1 = fold_bn_f64(b2[0].weight, None, b2[1])
+    wd, bd = fold_bn_f64(b2[3].weight, None, b2[4])
+    w2, bb2 = fold_bn_f64(b2[5].weight, None, b2[6])
+    vec = lambda b, n: _padded(b, (n,), (0,), torch.float32)
+    unit = ShuffleUnit(_padded(w1.flatten(1), (hp, kx), (0, col), dt), vec(b1, hp),
+                       _padded(wd.reshape(h, 9).t(), (9, hp), (0, 0), dt), vec(bd, hp),
+                       _padded(w2.flatten(1), (hp, hp), (0, 0), dt), vec(bb2, hp), cin, c, stride)
+    if stride == 2:
+        b = u.branch1
+        wd1, bd1 = fold_bn_f64(b[0].weight, None, b[1])
+        wp1, bp1 = fold_bn_f64(b[2].weight, None, b[3])
+        unit.wd1, unit.bd1 = _padded(wd1.reshape(cin, 9).t(), (9, kx), (0, 0), dt), vec(bd1, kx)
+        unit.wp1, unit.bp1 = _padded(wp1.flatten(1), (hp, kx), (0, 0), dt), vec(bp1, hp)
+    return unit
+
+
+def unpack_shuffle_unit(u: ShuffleUnit) -> dict:
+    """Inverse of pack_shuffle_unit's layouts -> fp32 conv weights (BN folded in) and biases at their logical sizes."""
+    h, cin = u.c // 2, u.cin
+    _, k0, _ = shuffle_dims(cin, u.c, u.stride, "fp32" if u.w1.dtype == torch.float32 else "fp16")
+    col, kin = (h - k0, h) if u.stride == 1 else (0, cin)
+    out = {"w1": u.w1[:h, col:col + kin].float().reshape(h, kin, 1, 1), "b1": u.b1[:h],
+           "wd": u.wd[:, :h].float().t().reshape(h, 1, 3, 3), "bd": u.bd[:h],
+           "w2": u.w2[:h, :h].float().reshape(h, h, 1, 1), "b2": u.b2[:h]}
+    if u.stride == 2:
+        out.update(wd1=u.wd1[:, :cin].float().t().reshape(cin, 1, 3, 3), bd1=u.bd1[:cin],
+                   wp1=u.wp1[:h, :cin].float().reshape(h, cin, 1, 1), bp1=u.bp1[:h])
+    return {k: v.contiguous() for k, v in out.items()}
+
+
 # Winograd F(2x2, 3x3) filter transform (Lavin & Gray): U = G g G^T
 WINO_G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 
@@ -940,6 +1033,16 @@ def compile_model(m: nn.Module, name: str, dtype: str = "fp16") -> Program:
         p.fcs[0].sw = None              # true fp32: no split path
         p.num_classes = m.classifier.out_features
         return p
+    if isinstance(m, ref.ShuffleNetV2):
+        if m.conv5[0].out_channels > 1280:
+            raise ValueError("ShuffleNetV2 is served up to x1.5: conv5 wider than 1280 (x2.0) is not")
+        p = Program(name, "shufflenet", stem=make_conv(m.conv1[0], m.conv1[1], True, dt), dtype=dt)
+        p.features = [("shuffle", pack_shuffle_unit(u, dt)) for st in (m.stage2, m.stage3, m.stage4) for u in st]
+        p.last = make_pw(m.conv5[0], m.conv5[1], 1, dt)
+        p.fcs = [make_fc(m.fc, False, dtype=dt)]
+        p.fcs[0].sw = None              # true fp32: no split path
+        p.num_classes = m.fc.out_features
+        return p
     raise TypeError(f"cannot compile {type(m).__name__}")
 
 
@@ -965,6 +1068,18 @@ def _emu_fire(f: Fire, x: torch.Tensor) -> torch.Tensor:
     s = _emu_conv(f.squeeze, x)
     return torch.cat([F.relu(F.conv2d(s, w1.to(x.device), f.be[:f.e1].to(x.device))),
                       F.relu(F.conv2d(s, w3.to(x.device), f.be[f.e1:].to(x.device), padding=1))], 1)
+
+
+def _emu_shuffle(u: ShuffleUnit, x: torch.Tensor) -> torch.Tensor:
+    w = {k: v.to(x.device) for k, v in unpack_shuffle_unit(u).items()}
+    h = u.c // 2
+    if u.stride == 1:
+        left, t = x.chunk(2, dim=1)
+    else:
+        left = F.conv2d(x, w["wd1"], w["bd1"], 2, 1, groups=u.cin)
+        left, t = F.relu(F.conv2d(left, w["wp1"], w["bp1"])), x
+    y = F.conv2d(F.relu(F.conv2d(t, w["w1"], w["b1"])), w["wd"], w["bd"], u.stride, 1, groups=h)
+    return ref.channel_shuffle(torch.cat([left, F.relu(F.conv2d(y, w["w2"], w["b2"]))], 1), 2)
 
 
 def _emu_conv(c: Conv, x: torch.Tensor, res: torch.Tensor | None = None) -> torch.Tensor:
@@ -1023,6 +1138,11 @@ def emulate(p: Program, img_u8: torch.Tensor) -> torch.Tensor:
                 w = v.w.float().reshape(v.cin // 2, v.cin, 1, 1).to(x.device)
                 x = F.avg_pool2d(F.conv2d(F.relu(aff(x, v.scale, v.shift)), w), 2, 2)
         x = F.relu(aff(x, *p.head_norm)).mean(dim=(2, 3))
+    elif p.kind == "shufflenet":
+        x = F.max_pool2d(_emu_conv(p.stem, x), 3, 2, 1)
+        for _, u in p.features:
+            x = _emu_shuffle(u, x)
+        x = _emu_conv(p.last, x).mean(dim=(2, 3))
     else:
         for k, v in p.features:
             x = _emu_conv(v, x) if k == "conv" else F.max_pool2d(x, *v)
@@ -1077,6 +1197,14 @@ def program_flops(p: Program, hw: int = 224) -> float:
             tot += h * h * v.flops_per_out_pixel
             if k == "transition":
                 h //= 2
+    elif p.kind == "shufflenet":
+        h = out_hw(hw, p.stem)
+        tot += h * h * p.stem.flops_per_out_pixel
+        h = (h + 2 - 3) // 2 + 1
+        for _, u in p.features:
+            f, h = u.flops(h)
+            tot += f
+        tot += h * h * p.last.flops_per_out_pixel
     else:
         h = hw
         for k, v in p.features:

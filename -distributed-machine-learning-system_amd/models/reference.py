@@ -436,6 +436,74 @@ def densenet201(num_classes=1000):
     return DenseNet((6, 12, 48, 32), num_classes=num_classes)
 
 
+def channel_shuffle(x, groups=2):
+    b, c, h, w = x.shape
+    return x.view(b, groups, c // groups, h, w).transpose(1, 2).reshape(b, c, h, w)
+
+
+class ShuffleUnit(nn.Module):
+    """torchvision's ShuffleNetV2 ``InvertedResidual``.  ``branch2``: 1x1-BN-ReLU, depthwise 3x3-BN (no activation),
+    1x1-BN-ReLU, on the second half of the channels at stride 1 and on all of them at stride 2; ``branch1``
+    (stride 2 only): depthwise 3x3-BN, 1x1-BN-ReLU.  Concat, then ``channel_shuffle(2)``."""
+
+    def __init__(self, cin, c, stride):
+        super().__init__()
+        h = c // 2
+        self.stride = stride
+        if stride == 1 and cin != c:
+            raise ValueError("a stride-1 unit keeps its width")
+        self.branch1 = nn.Sequential() if stride == 1 else nn.Sequential(
+            _conv(cin, cin, 3, 2, 1, groups=cin), nn.BatchNorm2d(cin), _conv(cin, h, 1), nn.BatchNorm2d(h),
+            nn.ReLU(inplace=True))
+        self.branch2 = nn.Sequential(
+            _conv(cin if stride == 2 else h, h, 1), nn.BatchNorm2d(h), nn.ReLU(inplace=True),
+            _conv(h, h, 3, stride, 1, groups=h), nn.BatchNorm2d(h), _conv(h, h, 1), nn.BatchNorm2d(h),
+            nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        if self.stride == 1:
+            x1, x2 = x.chunk(2, dim=1)
+            out = torch.cat((x1, self.branch2(x2)), dim=1)
+        else:
+            out = torch.cat((self.branch1(x), self.branch2(x)), dim=1)
+        return channel_shuffle(out, 2)
+
+
+class ShuffleNetV2(nn.Module):
+    """torchvision v0.10 ShuffleNetV2 (stages of 4, 8 and 4 units, 24-channel stem, 1024-wide conv5), its key names.
+    Parameters keep PyTorch's default initialisation, as torchvision's do."""
+
+    def __init__(self, widths, num_classes=1000):
+        super().__init__()
+        self.widths = tuple(widths)
+        self.conv1 = nn.Sequential(_conv(3, 24, 3, 2, 1), nn.BatchNorm2d(24), nn.ReLU(inplace=True))
+        self.maxpool = nn.MaxPool2d(3, 2, 1)
+        cin = 24
+        for name, n, c in zip(("stage2", "stage3", "stage4"), (4, 8, 4), widths):
+            setattr(self, name, nn.Sequential(*[ShuffleUnit(cin if i == 0 else c, c, 2 if i == 0 else 1)
+                                                for i in range(n)]))
+            cin = c
+        self.conv5 = nn.Sequential(_conv(cin, 1024, 1), nn.BatchNorm2d(1024), nn.ReLU(inplace=True))
+        self.fc = nn.Linear(1024, num_classes)
+
+    def forward(self, x):
+        x = self.maxpool(self.conv1(x))
+        x = self.conv5(self.stage4(self.stage3(self.stage2(x))))
+        return self.fc(x.mean(dim=(2, 3)))
+
+
+def shufflenet_v2_x0_5(num_classes=1000):
+    return ShuffleNetV2((48, 96, 192), num_classes)
+
+
+def shufflenet_v2_x1_0(num_classes=1000):
+    return ShuffleNetV2((116, 232, 464), num_classes)
+
+
+def shufflenet_v2_x1_5(num_classes=1000):
+    return ShuffleNetV2((176, 352, 704), num_classes)
+
+
 def resnet18(num_classes=1000):
     return ResNet(BasicBlock, [2, 2, 2, 2], num_classes)
 
@@ -476,14 +544,17 @@ def alexnet(num_classes=1000):
     return AlexNet(num_classes)
 
 
-# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2 / V3 + SqueezeNet
+# torchvision v0.10's ResNet family (the hub the reference loads from) + AlexNet + MobileNetV2 / V3 + SqueezeNet +
+# DenseNet + ShuffleNetV2 (not shufflenet_v2_x2_0: its 2048-wide conv5 is wider than conv1x1_narrow takes)
 BUILDERS = {"resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50, "alexnet": alexnet,
             "resnet101": resnet101, "resnet152": resnet152, "resnext50_32x4d": resnext50_32x4d,
             "resnext101_32x8d": resnext101_32x8d, "wide_resnet50_2": wide_resnet50_2,
             "wide_resnet101_2": wide_resnet101_2, "mobilenet_v2": mobilenet_v2,
             "mobilenet_v3_large": mobilenet_v3_large, "mobilenet_v3_small": mobilenet_v3_small,
             "squeezenet1_0": squeezenet1_0, "squeezenet1_1": squeezenet1_1,
-            "densenet121": densenet121, "densenet169": densenet169, "densenet201": densenet201}
+            "densenet121": densenet121, "densenet169": densenet169, "densenet201": densenet201,
+            "shufflenet_v2_x0_5": shufflenet_v2_x0_5, "shufflenet_v2_x1_0": shufflenet_v2_x1_0,
+            "shufflenet_v2_x1_5": shufflenet_v2_x1_5}
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -548,7 +619,11 @@ ALIASES = {"resnet": "resnet18", "resnet-18": "resnet18", "resnet_18": "resnet18
            "squeezenet": "squeezenet1_1", "squeezenet1.1": "squeezenet1_1", "squeezenet-1.1": "squeezenet1_1",
            "squeezenet1.0": "squeezenet1_0", "squeezenet-1.0": "squeezenet1_0",
            "densenet": "densenet121", "densenet-121": "densenet121", "densenet-169": "densenet169",
-           "densenet-201": "densenet201"}
+           "densenet-201": "densenet201",
+           "shufflenet": "shufflenet_v2_x1_0", "shufflenet_v2": "shufflenet_v2_x1_0",
+           "shufflenetv2_x0.5": "shufflenet_v2_x0_5", "shufflenetv2_x1.0": "shufflenet_v2_x1_0",
+           "shufflenetv2_x1.5": "shufflenet_v2_x1_5", "shufflenetv2-x0.5": "shufflenet_v2_x0_5",
+           "shufflenetv2-x1.0": "shufflenet_v2_x1_0", "shufflenetv2-x1.5": "shufflenet_v2_x1_5"}
 
 
 def canonical(name: str) -> str:

@@ -243,9 +243,10 @@ class HipRunner:
 
     # -- eager forward ------------------------------------------------------
     def _guarded(self) -> bool:
-        # MobileNetV2 / V3, SqueezeNet and DenseNet have no split path (their fp32 programs are true fp32), hence no
-        # range guard
-        return self.p.kind not in ("mobilenet", "mobilenet_v3", "squeezenet", "densenet") and self.p.dtype == "fp32" \
+        # MobileNetV2 / V3, SqueezeNet, DenseNet and ShuffleNetV2 have no split path (their fp32 programs are true
+        # fp32), hence no range guard
+        return self.p.kind not in ("mobilenet", "mobilenet_v3", "squeezenet", "densenet", "shufflenet") \
+            and self.p.dtype == "fp32" \
             and self.split and self._split_ok()
 
     def logits(self, img_u8: torch.Tensor, start: torch.Tensor | None = None, batch: int = -1,
@@ -317,6 +318,8 @@ class HipRunner:
             return self._logits_squeezenet(ims, native)
         if p.kind == "densenet":
             return self._logits_densenet(ims, native)
+        if p.kind == "shufflenet":
+            return self._logits_shufflenet(ims, native)
         if p.dtype == "fp32":
             return self._logits_f32(ims, native)
         s = p.stem
@@ -440,6 +443,20 @@ class HipRunner:
             else:
                 x = o.fire(x, v.squeeze.w, v.squeeze.b, v.we, v.be, v.e1)
         return o.conv1x1_relu_pool(x, p.last.w, p.last.b)
+
+    def _logits_shufflenet(self, ims: _Images, native):
+        """ShuffleNetV2 x0.5 / x1.0 / x1.5 in either precision (fp32: true fp32 on the f32 MFMA): NHWC4 producer ->
+        small-C stem conv with ReLU -> max pool -> ONE ops.shuffle_unit launch a unit (split, both 1x1s, the
+        depthwise 3x3, concat and channel shuffle; width 116 travels as 120 channels with a zero pad) -> conv5 on
+        the narrow 1x1 kernel (ReLU) -> average pool -> FC.  Everything on the current stream."""
+        o, p, s = self.ops, self.p, self.p.stem
+        x = self._nhwc4(ims, f32=p.dtype == "fp32") if native else o.resize_crop(ims.img, 256, 224)
+        x = o.maxpool2d(o.conv2d(x, s.w, s.b, s.kh, s.kw, s.stride, s.pad, True), 3, 2, 1)
+        for _, u in p.features:
+            x = o.shuffle_unit(x, u.w1, u.b1, u.wd, u.bd, u.w2, u.b2, u.stride, u.wd1, u.bd1, u.wp1, u.bp1, c=u.c)
+        x = o.conv1x1_narrow(x, p.last.w, p.last.b, p.last.act)
+        x = o.global_avgpool(x)
+        return o.linear(x, p.fcs[0].w, p.fcs[0].b, relu=False, out_f32=True)
 
     def _logits_densenet(self, ims: _Images, native):
         """DenseNet-121 / 169 / 201 in either precision (fp32: true fp32 on the f32 MFMA): NHWC4 producer ->

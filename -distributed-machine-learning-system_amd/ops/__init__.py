@@ -17,6 +17,7 @@ __all__ = [
     "conv3x3_grouped", "conv3x3_grouped_split", "conv3x3_grouped_f32", "conv3x3_grouped_ok",
     "conv3x3_dw", "conv1x1_narrow", "conv_dw", "se_excite", "fire", "fire_ok", "conv1x1_relu_pool",
     "dense_layer", "dense_layer_ok", "dense_plan", "dense_transition", "maxpool2d_into", "bn_relu_avgpool",
+    "shuffle_unit", "shuffle_unit_ok", "shuffle_plan",
     "conv1x1_dual", "conv1x1_dual_split", "conv1x1_fused_next", "conv2d_split", "conv2d_split_tail", "conv2d_split_tail_ok", "conv3x3_split_block", "conv3x3_split_block_ok", "linear_split", "stem_split", "stem_u8_f16", "alex_stem_split", "alex_stem_u8_f16", "preprocess_pack3_split", "conv2d_pack3_split", "split_from_f32", "f32_from_split", "maxpool2d_split", "pick_tile_split",
     "jpeg_parse", "jpeg_entropy_batch", "jpeg_plan", "jpeg_idct", "jpeg_resize_crop",
     "jpeg_huff_pack", "jpeg_entropy_zero", "jpeg_entropy_gpu", "jpeg_entropy_gpu_parallel", "jpeg_huff_par_rounds",
@@ -220,6 +221,32 @@ def bn_relu_avgpool(buf, scale, shift):
     """``mean over pixels of relu(buf scale + shift)`` -> [B, C] in ``buf``'s dtype: DenseNet's norm5 + ReLU + global
     average pool; fp32 sums in a fixed order, the same bits every run."""
     return load().bn_relu_avgpool(buf, scale, shift)
+
+
+def shuffle_unit(x, w1, b1, wd, bd, w2, b2, stride: int = 1, wd1=None, bd1=None, wp1=None, bp1=None, c=None, out=None):
+    """ShuffleNetV2 unit in ONE launch on NHWC [B, H, W, Cpin], fp16 or true fp32 by ``x``'s dtype (shuffle_unit.hip):
+    channel split, 1x1 + ReLU, depthwise 3x3 (bias, no activation), 1x1 + ReLU, concat and ``channel_shuffle(2)``.
+    Returns [B, Ho, Wo, Cp] in logical channel order, Cp = roundup(c, 8), pad channels zero.  Stride 1:
+    ``out[2i] = x[i]`` (bit-exact), ``out[2i + 1] = branch2(x[h:c])[i]`` with h = c / 2; stride 2 (Ho = (H - 1) // 2 + 1):
+    ``out[2i] = relu(wp1 dw(x) + bp1)[i]``, ``out[2i + 1] = branch2(x)[i]``.  Operands come from
+    models.packed.pack_shuffle_unit (``shuffle_plan`` has hp and Kx): ``w1`` [hp, Kx], ``wd`` [9, hp], ``w2`` [hp, hp],
+    ``wd1`` [9, Kx], ``wp1`` [hp, Kx], biases fp32; rows and columns outside the logical widths are zero, so input pad
+    channels reach nothing.  ``c``: the logical output width (default at stride 1: x's channels).  Anything else
+    raises and launches nothing."""
+    return load().shuffle_unit(x, w1, b1, wd, bd, w2, b2, int(stride), wd1, bd1, wp1, bp1, -1 if c is None else int(c),
+                               out)
+
+
+def shuffle_unit_ok(h: int, w: int, cin: int, c: int, stride: int) -> bool:
+    """Whether ``shuffle_unit`` takes this shape (in both precisions)."""
+    return bool(load().shuffle_unit_ok(int(h), int(w), int(cin), int(c), int(stride)))
+
+
+def shuffle_plan(h: int, w: int, cin: int, c: int, stride: int, f32: bool = False) -> dict:
+    """The plan ``shuffle_unit`` launches with (csrc/shuffle_math.h): output rows a band, bands an image, images a
+    workgroup, LDS bytes and the padded widths.  Host only, needs no GPU."""
+    keys = ("R", "bands", "imgs", "lds", "hp", "Kx", "Cp", "Cpin", "lds_whole")    # lds_whole: the image as one band
+    return dict(zip(keys, (int(v) for v in load().shuffle_plan(int(h), int(w), int(cin), int(c), int(stride), bool(f32)))))
 
 
 def preprocess_pack3_split(img_u8, kw: int, stride: int, pad: int, start=None, batch: int = -1,

@@ -54,7 +54,8 @@ log = logging.getLogger("idunno.elastic")
 MODEL_IDS = {"alexnet": 0, "resnet18": 1, "resnet50": 2, "resnet34": 3, "resnet101": 4, "resnet152": 5,
              "resnext50_32x4d": 6, "resnext101_32x8d": 7, "wide_resnet50_2": 8, "wide_resnet101_2": 9, "mobilenet_v2": 10,
              "mobilenet_v3_large": 11, "mobilenet_v3_small": 12, "squeezenet1_0": 13, "squeezenet1_1": 14,
-             "densenet121": 15, "densenet169": 16, "densenet201": 17}
+             "densenet121": 15, "densenet169": 16, "densenet201": 17,
+             "shufflenet_v2_x0_5": 18, "shufflenet_v2_x1_0": 19, "shufflenet_v2_x1_5": 20}
 MODEL_NAMES = {v: k for k, v in MODEL_IDS.items()}
 HDR_ROWS = 2        # (compute_us, model_id), (n_images, tag) at the end of every send buffer
 

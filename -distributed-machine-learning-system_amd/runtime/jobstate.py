@@ -45,7 +45,8 @@ DEFAULT_BATCHSIZE = {"resnet18": 400, "alexnet": 500, "resnet50": 1024, "resnet3
                      "resnet101": 400, "resnet152": 400, "resnext50_32x4d": 400, "resnext101_32x8d": 400,
                      "wide_resnet50_2": 400, "wide_resnet101_2": 400, "mobilenet_v2": 400,
                      "mobilenet_v3_large": 400, "mobilenet_v3_small": 400, "squeezenet1_0": 400, "squeezenet1_1": 400,
-                     "densenet121": 400, "densenet169": 400, "densenet201": 400}
+                     "densenet121": 400, "densenet169": 400, "densenet201": 400,
+                     "shufflenet_v2_x0_5": 400, "shufflenet_v2_x1_0": 400, "shufflenet_v2_x1_5": 400}
 
 
 def class_names(n: int = 1000, path: str | None = None) -> list[str]:
